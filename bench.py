@@ -12,12 +12,19 @@ Default workload (N=1): BASELINE.json configs[1] — 4,096 documents x 8 clients
 remove length U[1,8]).  Multi-GPU (torchrun): documents shard across ranks with
 no data-path collective (weak scaling); timing = max over ranks.
 
+A plain run sets up, warms up, times `--steps` steps and prints the result line
+(metric, value, ms_per_step, the roofline of the timed launches, status words).
+`--dump-outputs DIR` also writes what the last timed step left in the documents
+(DIR/<name>.npy, see dump_outputs).  Everything that takes work of its own moves
+behind `--full`: the SnapshotV1 pass and its timing, the oracle parity checks and
+the digest manifests, the CPU baseline and the host ingest legs.
+
 JSON fields beyond the driver contract:
   roofline      algorithmic HBM bytes per launch (SURVEY.md §8(d) B_op formula,
                 from the engine's per-document counters) / average replay-kernel
                 time measured with HIP events on the engine's stream;
-  cpu_baseline  the oracle (C++ restatement of the reference algorithm, "port")
-                replaying a bounded sample of the same streams on host threads.
+  cpu_baseline  (--full) the oracle (C++ restatement of the reference algorithm,
+                "port") replaying a bounded sample of the same streams on host threads.
 """
 import argparse
 import json
@@ -296,6 +303,57 @@ def manifest_text(m):
     return f"; MANIFEST MISMATCH: {m['mismatches']} of {m['of']} documents differ from the oracle's manifest"
 
 
+DUMP_BUDGET = 64 << 20          # bytes --dump-outputs may write in all
+DUMP_DOCS = 131072              # documents whose status, counters and digests are written (all, if fewer)
+DUMP_TEXT_DOCS = 32             # documents whose text is sampled
+DUMP_TEXT_UNITS = 4 << 20       # UTF-16 units the text sample holds at most (float32: 16 MB)
+
+
+def u64_halves(a):
+    """uint64 values as (high, low) 32-bit halves, one row each: exact in float64."""
+    a = np.asarray(a, np.uint64)
+    return np.stack([(a >> np.uint64(32)).astype(np.float64), (a & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=1)
+
+
+def doc_outputs(eng, n_docs, digs, seed):
+    """What the last timed step left in this engine's documents, as a caller reads it back:
+    status words, the §8(d) counters, SnapshotV1 digests (every byte of a document's snapshot
+    feeds its digest) and the text of a fixed, seeded sample of documents."""
+    rng = np.random.RandomState(seed & 0x7FFFFFFF)
+    docs = np.arange(n_docs)
+    if n_docs > DUMP_DOCS:
+        docs = np.sort(rng.permutation(n_docs)[:DUMP_DOCS])
+    cnt = eng.counters(docs)
+    out = {"docs": docs.astype(np.float64),
+           "status": eng.status(docs).astype(np.float64),
+           "counters": np.stack([cnt[k].astype(np.float64) for k in COUNTER_KEYS], axis=1),
+           "digests": u64_halves(np.asarray(digs, np.uint64)[docs])}
+    sample = np.sort(rng.permutation(n_docs)[:DUMP_TEXT_DOCS])
+    units, lens, kept = [], [], []
+    for d in sample:
+        u = np.frombuffer(eng.get_text([int(d)])[0].encode("utf-16-le", "surrogatepass"), np.uint16)
+        if sum(lens) + len(u) > DUMP_TEXT_UNITS:
+            break
+        units.append(u)
+        lens.append(len(u))
+        kept.append(int(d))
+    out["text_docs"] = np.asarray(kept, np.float64)
+    out["text_lengths"] = np.asarray(lens, np.float64)
+    out["text_units"] = np.concatenate(units).astype(np.float32) if units else np.zeros(0, np.float32)
+    return out
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one <name>.npy per array (float32 / float64), DUMP_BUDGET bytes at most."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET} budget")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def run_config4(args, c, world, rank, local):
     """Config 4: long documents.  Untimed: pre-build every document by
     c['prebuild'] appends (5 chars, segment props alternating between two sets,
@@ -315,7 +373,8 @@ def run_config4(args, c, world, rank, local):
                  window_per_doc=16384, text_per_doc=5 * pre + c["ins_len"] * ops + 4096,
                  propsets_per_doc=pre + ops + 64)
     set_residency(eng, args)
-    stage_ms = reserve_staging(eng)
+    snap = args.full or bool(args.dump_outputs)        # the SnapshotV1 pass after the timed steps
+    stage_ms = reserve_staging(eng) if snap else None
     eng.upload_props(ann_props())
     eng.upload_names(['"c%d"' % i for i in range(64)])
     seed = args.seed ^ (rank * 0x9E3779B1)
@@ -370,11 +429,15 @@ def run_config4(args, c, world, rank, local):
     st = eng.status(range(n))
     cnt = eng.counters(range(n))
     ok = (not st.any()) and int((cnt["msgs"] - cnt_a["msgs"]).sum()) == msgs
-    neg = np.full(n, -1, np.int32)
-    t1 = time.perf_counter()
-    digs = eng.snapshot_digests(range(n), neg, neg, threads=min(16, os.cpu_count() or 1))
-    snap_ms = (time.perf_counter() - t1) * 1e3
-    if world > 1:
+    digs, snap_ms = None, None
+    if snap:
+        neg = np.full(n, -1, np.int32)
+        t1 = time.perf_counter()
+        digs = eng.snapshot_digests(range(n), neg, neg, threads=min(16, os.cpu_count() or 1))
+        snap_ms = (time.perf_counter() - t1) * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, doc_outputs(eng, n, digs, args.seed))
+    if world > 1 and args.full:
         # every rank checks its own first documents against the oracle (untimed)
         k = min(2, n)
         _, odg, ost = cpu_baseline_config4(eng, c, pa, pb, max(1, min(16, (os.cpu_count() or 1) // world)), docs=k)
@@ -401,10 +464,13 @@ def run_config4(args, c, world, rank, local):
                      "traffic_source": traffic[1] if traffic else None, "kernel": REPLAY_KERNEL[args.residency],
                      "kernel_ms": kern_s * 1e3, "bytes_per_launch": bytes_per_launch},
         "parity": "status words clean" if ok else "STATUS ERROR",
-        "snapshot": {"docs": n, "ms": snap_ms, "digest_xor": f"{int(np.bitwise_xor.reduce(digs)):016x}",
-                     "staging_reserve_ms": stage_ms},
         "gen_seconds": gen_s,
     }
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return
+    out["snapshot"] = {"docs": n, "ms": snap_ms, "digest_xor": f"{int(np.bitwise_xor.reduce(digs)):016x}",
+                       "staging_reserve_ms": stage_ms}
     if world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"], odg, ost = cpu_baseline_config4(eng, c, pa, pb, min(16, os.cpu_count() or 1),
                                                              docs=min(n, args.parity_docs))
@@ -481,7 +547,8 @@ def run_config5(args, c, world, rank, local):
     sh = build_sharded(dist, device, fac, total_docs, args.seed, MtGenParams, gen_kw, names=names)
     setup_s = time.time() - t0
     eng = sh.engine
-    stage_ms = reserve_staging(eng)
+    snap = args.full or bool(args.dump_outputs)        # the SnapshotV1 pass + gather after the timed steps
+    stage_ms = reserve_staging(eng) if snap else None
     # corrupt exchange rows on any rank: every rank stops before replaying (no value published)
     xb = torch.tensor([int(sh.timings.get("exchange_bad_docs", 0))], dtype=torch.int64, device=device)
     if world > 1:
@@ -516,12 +583,20 @@ def run_config5(args, c, world, rank, local):
     st = eng.status(range(sh.n_docs))
     cnt = eng.counters(range(sh.n_docs))
     bytes_per_launch = algorithmic_bytes(cnt)
-    digs = sh.gather_digests(dist, device, threads=min(16, os.cpu_count() or 1))
+    digs = sh.gather_digests(dist, device, threads=min(16, os.cpu_count() or 1)) if snap else None
+    if args.dump_outputs and rank == 0:
+        # rank 0's own documents' state, and the digests gathered from every rank
+        arrays = doc_outputs(eng, sh.n_docs, sh.local_digests, args.seed)
+        arrays["docs"] = np.asarray(sh.owned, np.float64)[arrays["docs"].astype(np.int64)]   # global ids
+        if world > 1:
+            arrays["digests_all_ranks"] = u64_halves(digs)
+        dump_outputs(args.dump_outputs, arrays)
     xbad = int(sh.timings.get("exchange_bad_docs", 0))
     bad = torch.tensor([int(st.any()) + int(int(cnt["msgs"].sum()) != my_msgs), xbad, sh.n_docs],
                        dtype=torch.int64, device=device)
     if world > 1:
         dist.all_reduce(bad)
+    if world > 1 and args.full:
         # every rank checks a sample of its own documents against the oracle (untimed)
         pb_, pc_ = config5_rank_parity(args, c, sh) if not args.no_cpu_baseline else (0, 0)
         par = torch.tensor([pb_, pc_], dtype=torch.int64, device=device)
@@ -559,14 +634,20 @@ def run_config5(args, c, world, rank, local):
                              "arrival by the owning rank (mt_generated_pack_rows / mt_upload_rows_dev)"},
         "memory": {"engine_pools_gb": eng.pool_bytes() / 1e9,
                    "exchange_buffers_peak_gb": (torch.cuda.max_memory_allocated(device) / 1e9) if device.type == "cuda" else None},
-        "snapshot": {"docs": sh.n_docs, "ms": sh.timings.get("snapshot_ms"), "host_threads": min(16, os.cpu_count() or 1),
-                     "staging_reserve_ms": stage_ms,
-                     "note": "rank 0's mt_snapshot_digests (staged download + SnapshotV1 JSON + xxh64), before the gather"},
         "sharding": {"rebalance_ms": sh.timings.get("rebalance_ms"), "rebalance_bytes": sh.timings.get("rebalance_bytes"),
-                     "digest_gather_ms": sh.timings.get("digest_ms"), "ingest_generate_s": sh.timings.get("generate_s"),
-                     "setup_s": setup_s, "digest_xor": f"{int(np.bitwise_xor.reduce(digs)):016x}",
+                     "ingest_generate_s": sh.timings.get("generate_s"), "setup_s": setup_s,
                      "docs_per_rank_max": int(np.bincount(sh.owner).max())},
     }
+    if not args.full:
+        if int(bad[1].item()):
+            out["parity"] = f"EXCHANGE CHECKSUM MISMATCH on {int(bad[1].item())} docs; " + out["parity"]
+        print(json.dumps(out), flush=True)
+        return
+    out["snapshot"] = {"docs": sh.n_docs, "ms": sh.timings.get("snapshot_ms"), "host_threads": min(16, os.cpu_count() or 1),
+                       "staging_reserve_ms": stage_ms,
+                       "note": "rank 0's mt_snapshot_digests (staged download + SnapshotV1 JSON + xxh64), before the gather"}
+    out["sharding"].update(digest_gather_ms=sh.timings.get("digest_ms"),
+                           digest_xor=f"{int(np.bitwise_xor.reduce(digs)):016x}")
     if not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline_config5(args, c, local)
         if int(bad[0].item()) == 0:
@@ -601,6 +682,7 @@ def run_config5_shares(args, c, local):
     names = ['"c%d"' % i for i in range(64)]
     fac = lambda n, caps: Host.engine(n, local, per_doc=caps)
     digs = np.zeros(total_docs, np.uint64)
+    snap = args.full or bool(args.dump_outputs)        # the SnapshotV1 pass after each share's timed steps
     shares, msgs_all, bad = [], 0, 0
     t_setup = time.time()
     for r, sh in rank_shares(device, fac, total_docs, world, args.seed, MtGenParams, gen_kw, names=names):
@@ -628,8 +710,9 @@ def run_config5_shares(args, c, local):
         cnt = eng.counters(range(sh.n_docs))
         ok = (not st.any()) and int(cnt["msgs"].sum()) == my_msgs
         bad += int(not ok)
-        neg = np.full(sh.n_docs, -1, np.int32)
-        digs[sh.owned] = eng.snapshot_digests(range(sh.n_docs), neg, neg, threads=min(16, os.cpu_count() or 1))
+        if snap:
+            neg = np.full(sh.n_docs, -1, np.int32)
+            digs[sh.owned] = eng.snapshot_digests(range(sh.n_docs), neg, neg, threads=min(16, os.cpu_count() or 1))
         shares.append({"rank": r, "docs": sh.n_docs, "msgs": my_msgs, "msgs_max": int(sh.ops.max()),
                        "ms_per_step": dt * 1e3, "kernel_ms": float(np.mean(kms)),
                        "exchange_bytes": sh.timings.get("rebalance_bytes"),
@@ -650,9 +733,13 @@ def run_config5_shares(args, c, local):
                    "msgs_total": msgs_all, "residency": args.residency},
         "shares": shares,
         "parity": "status words clean on every share" if bad == 0 else f"STATUS ERROR on {bad} shares",
-        "setup_s": gen_s, "digest_xor": f"{int(np.bitwise_xor.reduce(digs)):016x}",
+        "setup_s": gen_s,
     }
-    if bad == 0:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"digests": u64_halves(digs)})    # global document order
+    if args.full:
+        out["digest_xor"] = f"{int(np.bitwise_xor.reduce(digs)):016x}"
+    if args.full and bad == 0:
         name = "config5_1m" if total_docs == 1048576 else "config5"
         man = manifest_parity(name, digs, seed=args.seed, docs=total_docs, msgs_total=msgs_all)
         if man is not None:
@@ -921,6 +1008,12 @@ def _main(argv=None):
     ap.add_argument("--docs", type=int, default=0, help="override documents per GPU")
     ap.add_argument("--ops", type=int, default=0, help="override messages per document")
     ap.add_argument("--seed", type=int, default=20241015)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything that is not the headline figure: the SnapshotV1 "
+                         "pass, oracle parity and digest manifests, the CPU baseline, the host ingest legs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step left in the documents as DIR/<name>.npy (status words, "
+                         "counters, SnapshotV1 digests, a seeded sample of texts)")
     ap.add_argument("--prebuild", type=int, default=0, help="config4: override pre-build appends per document")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--parity-docs", type=int, default=0,
@@ -996,7 +1089,8 @@ def _main(argv=None):
         caps[k] = int(v)
     eng = Host.engine(c["docs"], local, **caps)
     set_residency(eng, args)
-    stage_ms = reserve_staging(eng)
+    snap = args.full or bool(args.dump_outputs)        # the SnapshotV1 pass after the timed steps
+    stage_ms = reserve_staging(eng) if snap else None
     big = c.get("big_min_ops", 0) if args.big_min_ops < 0 else args.big_min_ops
     if args.residency == "blk" and big:
         eng.set_size_class(big)
@@ -1058,18 +1152,23 @@ def _main(argv=None):
         # where each hand-over happened: the op index within its run (the rest ran from HBM)
         handover = {"docs": int(len(ho)), "at_op": [int(cur[d] - d * c["ops"]) for d in ho[:16]]}
     # SnapshotV1 of every document at its current window (reported, not timed as ops)
-    t1 = time.perf_counter()
+    digs, snap_ms, dig_xor = np.zeros(1, np.uint64), None, 0
     sthreads = min(16, os.cpu_count() or 1)
-    neg = np.full(c["docs"], -1, np.int32)
-    digs = eng.snapshot_digests(range(c["docs"]), neg, neg, threads=sthreads) if eng.fn["snapshot_digests"] else np.zeros(1, np.uint64)
-    snap_ms = (time.perf_counter() - t1) * 1e3
-    dig_xor = int(np.bitwise_xor.reduce(digs)) if len(digs) else 0
+    if snap:
+        t1 = time.perf_counter()
+        neg = np.full(c["docs"], -1, np.int32)
+        if eng.fn["snapshot_digests"]:
+            digs = eng.snapshot_digests(range(c["docs"]), neg, neg, threads=sthreads)
+        snap_ms = (time.perf_counter() - t1) * 1e3
+        dig_xor = int(np.bitwise_xor.reduce(digs)) if len(digs) else 0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, doc_outputs(eng, c["docs"], digs, args.seed))
     ok = (not st.any()) and int(cnt2["msgs"].sum()) == msgs
     total_msgs = msgs * world * args.steps
     value = total_msgs / dt
     kern_s = float(np.mean(kms)) / 1e3
     achieved = bytes_per_launch / kern_s / 1e9 if kern_s > 0 else 0.0
-    if world > 1:
+    if world > 1 and args.full:
         # every rank checks its own documents against the oracle (untimed), rank 0 reports the sum
         k = min(PARITY_DOCS, c["docs"])
         _, _, odg, ost = oracle_run(eng, c, MtGenParams, seed, k, max(1, min(16, (os.cpu_count() or 1) // world)))
@@ -1105,11 +1204,14 @@ def _main(argv=None):
                      "bytes_per_launch": bytes_per_launch},
         "hbm_gbps_algorithmic": achieved,
         "parity": "status words clean" if ok else "STATUS ERROR",
-        "snapshot": {"docs": c["docs"], "ms": snap_ms, "host_threads": sthreads, "digest_xor": f"{dig_xor:016x}",
-                     "staging_reserve_ms": stage_ms,
-                     "note": "mt_snapshot_digests after the timed steps: staged download + SnapshotV1 JSON + xxh64"},
         "gen_seconds": gen_s,
     }
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return
+    out["snapshot"] = {"docs": c["docs"], "ms": snap_ms, "host_threads": sthreads, "digest_xor": f"{dig_xor:016x}",
+                       "staging_reserve_ms": stage_ms,
+                       "note": "mt_snapshot_digests after the timed steps: staged download + SnapshotV1 JSON + xxh64"}
     if world == 1 and not args.no_cpu_baseline:
         threads = min(16, os.cpu_count() or 1)
         out["cpu_baseline"], odg, ost = cpu_baseline(eng, c, MtGenParams, seed, args.cpu_seconds, threads)

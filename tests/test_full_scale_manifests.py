@@ -2,7 +2,7 @@
 configs 3, 4 and 5 exactly as its measurement does (every document of the workload, the same
 seeds) and every document's SnapshotV1 digest must equal the oracle-made manifest
 (tests/golden/digests, tools/make_digest_manifest.py: the oracle's own generator and replay).
-Config 2's is checked by the default bench line itself.  These run in the -m gpu suite so the
+Config 2's is checked by the default `bench.py --full` line itself.  These run in the -m gpu suite so the
 round-end GPU tier checks configs 3-5 at full size, not only down-scaled."""
 import json
 import os
@@ -22,7 +22,7 @@ CASES = {
 
 def bench_line(cfg: str) -> dict:
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--steps", "1", "--warmup", "0",
-                        "--no-cpu-baseline", "--no-ingest"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--full", "--no-cpu-baseline", "--no-ingest"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

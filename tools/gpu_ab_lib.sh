@@ -12,7 +12,7 @@ fi
 for c in "$@"; do
   for v in prod alt; do
     L=""; [ $v = alt ] && L=$ALT
-    MTGPU_LIB=$L timeout -k 10 300 python -u bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-ingest > $OUT/${c}_$v.json 2> $OUT/${c}_$v.err || { echo FAIL $c $v; tail -20 $OUT/${c}_$v.err; exit 1; }
+    MTGPU_LIB=$L timeout -k 10 300 python -u bench.py --full --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-ingest > $OUT/${c}_$v.json 2> $OUT/${c}_$v.err || { echo FAIL $c $v; tail -20 $OUT/${c}_$v.err; exit 1; }
     python -c "import json;d=json.load(open('$OUT/${c}_$v.json'));print('$c $v', round(d['value']/1e6,3), 'M ops/s', round(d['roofline']['kernel_ms'],1), 'ms', d.get('parity'))"
   done
 done

@@ -11,6 +11,6 @@ timeout -k 10 300 python -u -m pytest -x -q --timeout 120 --timeout-method threa
 rc=$?; echo "tests rc=$rc"; tail -1 $OUT/pytest.log; [ $rc -eq 0 ] || exit $rc
 for p in $SPLITS; do
   n=${p/:/_}
-  timeout -k 10 400 python -u bench.py --config config5 --steps 3 --warmup 1 --no-cpu-baseline --no-ingest --partition $p > $OUT/config5_$n.json 2> $OUT/config5_$n.err || { echo FAIL $p; tail -5 $OUT/config5_$n.err; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --config config5 --steps 3 --warmup 1 --no-cpu-baseline --no-ingest --partition $p > $OUT/config5_$n.json 2> $OUT/config5_$n.err || { echo FAIL $p; tail -5 $OUT/config5_$n.err; exit 1; }
   python -c "import json;d=json.load(open('$OUT/config5_$n.json'));print('config5 $p', round(d['value']/1e6,2), 'M ops/s', round(d['ms_per_step'],1), 'ms', d['parity'])"
 done

@@ -12,7 +12,7 @@ mkdir -p $O
 export PYTHONUNBUFFERED=1
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 for c in $CFGS; do
-  B="bench.py --config $c"
+  B="bench.py --full --config $c"
   K=mt_replay_blk_kernel; KS=$K
   [ $c = config4 ] && K=mt_replay_big_kernel && KS=$K
   [ $c = config5 ] && K="mt_replay_blkw_kernel+mt_replay_blk_kernel" && KS=mt_replay_blkw_kernel

@@ -13,7 +13,7 @@ mkdir -p $O
 export PYTHONUNBUFFERED=1
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 for c in $CFGS; do
-  B="bench.py --config $c"
+  B="bench.py --full --config $c"
   K=mt_replay_blk_kernel; [ $c = config4 ] && K=mt_replay_big_kernel
   timeout -k 10 500 python $B > $O/${c}_bench.json 2> $O/${c}_bench.err || { echo BENCH_FAIL $c; tail -20 $O/${c}_bench.err; exit 1; }
   cat $O/${c}_bench.json

@@ -9,12 +9,12 @@ for r in 1 2; do
   for lib in fluidframework_amd/libmtgpu_r05.so fluidframework_amd/libmtgpu.so; do
     for c in config2 config4; do
       n=$(basename $lib .so)_${c}_$r
-      MTGPU_LIB=$lib timeout -k 10 300 python -u bench.py --config $c --steps 5 --warmup 1 --no-cpu-baseline --no-ingest --partition off > $O/$n.json 2> $O/$n.err || { echo FAIL $n; tail -20 $O/$n.err; exit 1; }
+      MTGPU_LIB=$lib timeout -k 10 300 python -u bench.py --full --config $c --steps 5 --warmup 1 --no-cpu-baseline --no-ingest --partition off > $O/$n.json 2> $O/$n.err || { echo FAIL $n; tail -20 $O/$n.err; exit 1; }
       python -c "import json;d=json.load(open('$O/$n.json'));print('$n', round(d['value']/1e6,2), 'M ops/s', round(d['ms_per_step'],1), 'ms', d['parity'][-24:])"
     done
   done
 done
-timeout -k 10 900 python -u bench.py > $O/bench_default.json 2> $O/bench_default.err || { echo FAIL bench; tail -20 $O/bench_default.err; exit 1; }
+timeout -k 10 900 python -u bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { echo FAIL bench; tail -20 $O/bench_default.err; exit 1; }
 python -c "
 import json; d=json.load(open('$O/bench_default.json'))
 print('default', round(d['value']/1e6,2), 'M ops/s', round(d['ms_per_step'],2), 'ms', d['parity'][-50:])

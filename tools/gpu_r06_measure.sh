@@ -11,7 +11,7 @@ export PYTHONUNBUFFERED=1
 timeout -k 10 400 python -u -m pytest -x -v --timeout 300 --timeout-method thread -m gpu tests/test_full_scale_manifests.py \
     > $O/pytest_manifests.txt 2>&1 || { echo FAIL manifests; tail -30 $O/pytest_manifests.txt; exit 1; }
 tail -3 $O/pytest_manifests.txt
-timeout -k 10 900 python -u bench.py > $O/bench_default.json 2> $O/bench_default.err || { echo FAIL bench; tail -20 $O/bench_default.err; exit 1; }
+timeout -k 10 900 python -u bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { echo FAIL bench; tail -20 $O/bench_default.err; exit 1; }
 python -c "
 import json; d=json.load(open('$O/bench_default.json'))
 print('default', round(d['value']/1e6,2), 'M ops/s', round(d['ms_per_step'],2), 'ms', d['parity'][-50:])

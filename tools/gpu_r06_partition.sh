@@ -9,19 +9,19 @@ timeout -k 10 300 python -u -m pytest -x -q --timeout 120 --timeout-method threa
     > $OUT/pytest_gpu.txt 2>&1 || { echo FAIL pytest; tail -30 $OUT/pytest_gpu.txt; exit 1; }
 tail -2 $OUT/pytest_gpu.txt
 summ() { python -c "import json;d=json.load(open('$1'));print('$2', round(d['value']/1e6,2), 'M ops/s', round(d['ms_per_step'],1), 'ms', d['config'].get('partition'), d['parity'][-48:])"; }
-timeout -k 10 400 python -u bench.py --config config5 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/c5_auto.json 2> $OUT/c5_auto.err \
+timeout -k 10 400 python -u bench.py --full --config config5 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/c5_auto.json 2> $OUT/c5_auto.err \
     || { echo FAIL c5; tail -20 $OUT/c5_auto.err; exit 1; }
 summ $OUT/c5_auto.json "c5 131072 auto"
 for t in "$@"; do
   n=${t/:/_}
-  timeout -k 10 400 python -u bench.py --config config5 --steps 3 --warmup 1 --no-cpu-baseline --partition $t > $OUT/c5_$n.json 2> $OUT/c5_$n.err \
+  timeout -k 10 400 python -u bench.py --full --config config5 --steps 3 --warmup 1 --no-cpu-baseline --partition $t > $OUT/c5_$n.json 2> $OUT/c5_$n.err \
       || { echo FAIL $t; tail -20 $OUT/c5_$n.err; exit 1; }
   summ $OUT/c5_$n.json "c5 131072 $t"
 done
-timeout -k 10 420 python -u bench.py --config config5 --docs 1048576 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/c5_1m_auto.json 2> $OUT/c5_1m_auto.err \
+timeout -k 10 420 python -u bench.py --full --config config5 --docs 1048576 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/c5_1m_auto.json 2> $OUT/c5_1m_auto.err \
     || { echo FAIL 1m; tail -20 $OUT/c5_1m_auto.err; exit 1; }
 summ $OUT/c5_1m_auto.json "c5 1M auto"
-timeout -k 10 600 python -u bench.py --config config5 --shares 8 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/c5_1m_shares8.json 2> $OUT/c5_1m_shares8.err \
+timeout -k 10 600 python -u bench.py --full --config config5 --shares 8 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/c5_1m_shares8.json 2> $OUT/c5_1m_shares8.err \
     || { echo FAIL shares; tail -20 $OUT/c5_1m_shares8.err; exit 1; }
 python -c "
 import json;d=json.load(open('$OUT/c5_1m_shares8.json'))

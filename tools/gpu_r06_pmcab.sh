@@ -12,7 +12,7 @@ for lib in "$@"; do
   for c in ${CFGS:-config2}; do
     n=$(basename $lib .so)_${c}
     K=mt_replay_blk_kernel; [ $c = config4 ] && K=mt_replay_big_kernel
-    B="bench.py --config $c --steps 1 --warmup 0 --no-cpu-baseline --no-ingest --partition off"
+    B="bench.py --full --config $c --steps 1 --warmup 0 --no-cpu-baseline --no-ingest --partition off"
     MTGPU_LIB=$lib timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/${n}_pmcF -o pmcF -- python $B > $O/${n}_pmcF.json 2> $O/${n}_pmcF.err || { echo PMCF_FAIL $n; tail -5 $O/${n}_pmcF.err; exit 1; }
     MTGPU_LIB=$lib timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/${n}_pmcW -o pmcW -- python $B > $O/${n}_pmcW.json 2> $O/${n}_pmcW.err || { echo PMCW_FAIL $n; tail -5 $O/${n}_pmcW.err; exit 1; }
     D=$(python -c "import json;d=json.load(open('$O/${n}_pmcF.json'));print(d['config']['docs_per_gpu'], d['config'].get('msgs_per_doc', 0))")

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 CFGS="config2 config5" ROUNDS=1 bash tools/gpu_lib_ab.sh ${1:-wab}/ab $A $B || exit 1
 for lib in $A $B; do
   n=$(basename $lib .so)
-  MTGPU_LIB=$lib timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/${n}_pmcW -o pmcW -- python bench.py --config config2 --steps 1 --warmup 0 --no-cpu-baseline --no-ingest > $O/${n}_pmcW.json 2> $O/${n}_pmcW.err || { echo PMCW_FAIL $n; tail -5 $O/${n}_pmcW.err; exit 1; }
+  MTGPU_LIB=$lib timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/${n}_pmcW -o pmcW -- python bench.py --full --config config2 --steps 1 --warmup 0 --no-cpu-baseline --no-ingest > $O/${n}_pmcW.json 2> $O/${n}_pmcW.err || { echo PMCW_FAIL $n; tail -5 $O/${n}_pmcW.err; exit 1; }
   python -c "
 import csv,sys
 sys.path.insert(0,'tools')
