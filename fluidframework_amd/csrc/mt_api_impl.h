@@ -165,6 +165,13 @@ const char* MT_FN(last_error)(mt_ctx* c) { return c ? c->err.c_str() : "null con
 __attribute__((used)) const char MT_FN(source_hash_tag)[] = "mt-src-hash:" MT_SRC_HASH;
 const char* MT_FN(source_hash)(void) { return MT_FN(source_hash_tag) + 12; }
 
+// Bytes of the pools allocated for `t` elements each and D documents.
+static uint64_t mt_pool_bytes_of(const MtDocLayout& t, size_t D) {
+    return sizeof(MtRow) * t.row + sizeof(MtBlk) * t.blk + sizeof(MtHeapE) * t.heap + 12ull * t.win + 4ull * t.anc +
+           2ull * t.text + sizeof(MtPSet) * t.pset +
+           (sizeof(MtDocHdr) + 4ull * MT_RFL + sizeof(MtDocLayout) + sizeof(MtOvx) * MT_OVX_CAP + sizeof(MtReg) * MT_REG_CAP) * D +
+           4ull * t.mid + 4ull * t.regr;
+}
 // Pools of every document, laid out back to back with per-document capacities.
 static void mt_caps_default(mt_limits& q) {
     if (!q.rows_per_doc) q.rows_per_doc = 4096;
@@ -221,11 +228,8 @@ static int mt_create_impl(int device, uint32_t n_docs, const mt_limits* caps, bo
     S.layout = (const MtDocLayout*)p;
     mtb_h2d(c, p, c->layout_h.data(), sizeof(MtDocLayout) * D);
     mtb_memset(S.hdr, 0, sizeof(MtDocHdr) * D);
-    c->tot = tot;
-    c->pool_bytes = sizeof(MtRow) * tot.row + sizeof(MtBlk) * tot.blk + sizeof(MtHeapE) * tot.heap + 12ull * tot.win +
-                    4ull * tot.anc + 2ull * tot.text + sizeof(MtPSet) * tot.pset +
-                    (sizeof(MtDocHdr) + 4ull * MT_RFL + sizeof(MtDocLayout) + sizeof(MtOvx) * MT_OVX_CAP +
-                     sizeof(MtReg) * MT_REG_CAP) * D + 4ull * tot.mid + 4ull * tot.regr;
+    c->tot = tot; c->cap = tot;
+    c->pool_bytes = mt_pool_bytes_of(tot, D);
     return MT_OK;
 }
 
@@ -242,8 +246,8 @@ int MT_FN(create_docs)(int device, uint32_t n_docs, const mt_limits* per_doc, mt
 // a summary to resume from (SURVEY.md §5 checkpoint/resume), used by benchmarks
 // that replay the same stream on the same starting state.
 struct MtCkPart { void** ck; void* live; size_t bytes; };
-static std::vector<MtCkPart> mt_ck_parts(mt_ctx* c) {
-    const MtState& S = c->S; const MtDocLayout& t = c->tot; const size_t D = S.maxDocs;
+static std::vector<MtCkPart> mt_ck_parts(mt_ctx* c, const MtDocLayout& t) {
+    const MtState& S = c->S; const size_t D = S.maxDocs;
     return {{&c->ck_rows, S.rows, sizeof(MtRow) * t.row}, {&c->ck_blk, S.blk, sizeof(MtBlk) * t.blk},
             {&c->ck_heap, S.heap, sizeof(MtHeapE) * t.heap}, {&c->ck_win, S.win, 4ull * t.win},
             {&c->ck_text, S.text, 2ull * t.text}, {&c->ck_pset, S.pset, sizeof(MtPSet) * t.pset},
@@ -251,27 +255,291 @@ static std::vector<MtCkPart> mt_ck_parts(mt_ctx* c) {
             {&c->ck_ovx, S.ovx, sizeof(MtOvx) * MT_OVX_CAP * D}, {&c->ck_mid, S.mid, 4ull * t.mid},
             {&c->ck_reg, S.reg, sizeof(MtReg) * MT_REG_CAP * D}, {&c->ck_regr, S.regr, 4ull * t.regr}};
 }
+static int mt_rederive(mt_ctx* c);
+static int mt_delta_size(mt_ctx* c, uint64_t capacity);
+// The pools up to their tails (documents relocated since the last checkpoint may have moved
+// them: the shadows grow with them), and the host's layout beside them.
 int MT_FN(checkpoint)(mt_ctx* c) {
     if (!c) return MT_E_INVALID;
     int rc = mtb_sync(c);
     if (rc) return rc;
-    for (auto& p : mt_ck_parts(c)) {
-        if (!*p.ck && mtb_malloc(p.ck, p.bytes ? p.bytes : 16) != 0) { c->err = "checkpoint allocation failed"; return MT_E_OOM; }
+    c->ck_valid = false;
+    size_t k = 0;
+    for (auto& p : mt_ck_parts(c, c->tot)) {
+        const size_t want = p.bytes ? p.bytes : 16;
+        if (*p.ck && c->ck_bytes[k] < want) { mtb_free(*p.ck); *p.ck = nullptr; c->ck_bytes[k] = 0; }
+        if (!*p.ck) {
+            if (mtb_malloc(p.ck, want) != 0) { *p.ck = nullptr; c->err = "checkpoint allocation failed"; return MT_E_OOM; }
+            c->ck_bytes[k] = want;
+        }
         if (p.bytes) mtb_d2d(c, *p.ck, p.live, p.bytes);
+        k++;
     }
+    c->ck_layout = c->layout_h; c->ck_tot = c->tot; c->ck_dead = c->dead;
     c->ck_valid = true;
     return MT_OK;
 }
+// Documents, layout table and tails as of the checkpoint: a pool reallocated since holds the
+// shadow as its prefix; slices handed out since are free again.
 int MT_FN(restore)(mt_ctx* c) {
     if (!c || !c->ck_valid) return MT_E_INVALID;
     int rc = mtb_sync(c);
     if (rc) return rc;
-    for (auto& p : mt_ck_parts(c)) if (p.bytes) mtb_d2d(c, p.live, *p.ck, p.bytes);
-    return MT_OK;
+    for (auto& p : mt_ck_parts(c, c->ck_tot)) if (p.bytes) mtb_d2d(c, p.live, *p.ck, p.bytes);
+    if (c->layout_h.size() == c->ck_layout.size() &&
+        memcmp(c->layout_h.data(), c->ck_layout.data(), sizeof(MtDocLayout) * c->layout_h.size()) != 0) {
+        c->layout_h = c->ck_layout;
+        mtb_h2d(c, (void*)c->S.layout, c->layout_h.data(), sizeof(MtDocLayout) * c->layout_h.size());
+        rc = mt_rederive(c);
+    }
+    c->tot = c->ck_tot; c->dead = c->ck_dead;
+    return rc;
 }
 int MT_FN(pool_bytes)(mt_ctx* c, uint64_t* bytes) {
     if (!c || !bytes) return MT_E_INVALID;
     *bytes = c->pool_bytes;
+    return MT_OK;
+}
+
+/* ------------------------------------------------------------- growth ---- */
+#ifndef MTB_HAVE_RELOCATE
+// A backend whose pools the host addresses (the emulation) takes these plain per-document
+// loops; the HIP backend defines its own over the kernels and MTB_HAVE_RELOCATE.
+static int mtb_launch_occupancy(mt_ctx* c, const uint32_t* docs, MtOcc* out, uint32_t n, uint32_t epoch) {
+    for (uint32_t i = 0; i < n; i++) { MtScratch sc; MtEng e; e.bind(c->S, docs[i], &sc); out[i] = mt_doc_occupancy(e, epoch); }
+    return MT_OK;
+}
+static int mtb_launch_relocate(mt_ctx* c, const uint32_t* docs, const MtDocLayout* ny, uint32_t n, uint32_t epoch, bool compact) {
+    for (uint32_t i = 0; i < n; i++) { MtScratch sc; MtEng e; e.bind(c->S, docs[i], &sc); mt_relocate_doc(e, c->S, ny[i], epoch, compact); }
+    return MT_OK;
+}
+#endif
+// The per-document pools: element size and the MtDocLayout field that counts its elements
+// (uid and udelta are laid out as the window is).
+struct MtPoolDesc { void* p; size_t esz; unsigned long long MtDocLayout::*n; const char* name; };
+static std::vector<MtPoolDesc> mt_pools(mt_ctx* c) {
+    const MtState& S = c->S;
+    return {{S.rows, sizeof(MtRow), &MtDocLayout::row, "rows"}, {S.blk, sizeof(MtBlk), &MtDocLayout::blk, "blocks"},
+            {S.heap, sizeof(MtHeapE), &MtDocLayout::heap, "heap"}, {S.win, 4, &MtDocLayout::win, "window"},
+            {S.uid, 4, &MtDocLayout::win, "window"}, {S.udelta, 4, &MtDocLayout::win, "window"},
+            {S.uanc, 4, &MtDocLayout::anc, "window"}, {S.text, 2, &MtDocLayout::text, "text"},
+            {S.pset, sizeof(MtPSet), &MtDocLayout::pset, "property sets"}, {S.mid, 4, &MtDocLayout::mid, "markers"},
+            {S.regr, 4, &MtDocLayout::regr, "register rows"}};
+}
+static void mt_set_pools(mt_ctx* c, const std::vector<MtPoolDesc>& P) {
+    MtState& S = c->S;
+    S.rows = (MtRow*)P[0].p; S.blk = (MtBlk*)P[1].p; S.heap = (MtHeapE*)P[2].p; S.win = (int*)P[3].p; S.uid = (int*)P[4].p;
+    S.udelta = (int*)P[5].p; S.uanc = (int*)P[6].p; S.text = (uint16_t*)P[7].p; S.pset = (MtPSet*)P[8].p; S.mid = (int*)P[9].p;
+    S.regr = (int*)P[10].p;
+}
+static unsigned long long MtDocLayout::*const MT_LY_OFF[9] = {&MtDocLayout::row, &MtDocLayout::blk, &MtDocLayout::heap,
+    &MtDocLayout::win, &MtDocLayout::anc, &MtDocLayout::text, &MtDocLayout::pset, &MtDocLayout::mid, &MtDocLayout::regr};
+// Elements a document of capacities y takes of each pool (in the offset fields).
+static MtDocLayout mt_slice(const MtDocLayout& y) {
+    MtDocLayout s{};
+    s.row = y.rowCap; s.blk = y.blkCap; s.heap = (unsigned long long)y.heapCap + 1; s.win = y.winCap;
+    s.anc = (unsigned long long)y.winCap * MT_MAXH; s.text = 2ull * y.textCap; s.pset = y.psetCap; s.mid = y.midCap;
+    s.regr = 2ull * y.regCap;
+    return s;
+}
+// Everything the library derives from the documents' capacities: the per-pool maxima, the
+// pools' bytes and the capture buffers' minimum sizes (staging sizes are taken per call).
+static int mt_rederive(mt_ctx* c) {
+    MtState& S = c->S;
+    S.rowCap = S.blkCap = S.heapCap = S.winCap = S.textCap = S.psetCap = 0;
+    for (const MtDocLayout& y : c->layout_h) {
+        S.rowCap = std::max(S.rowCap, y.rowCap); S.blkCap = std::max(S.blkCap, y.blkCap); S.heapCap = std::max(S.heapCap, y.heapCap);
+        S.winCap = std::max(S.winCap, y.winCap); S.textCap = std::max(S.textCap, y.textCap); S.psetCap = std::max(S.psetCap, y.psetCap);
+    }
+    c->pool_bytes = mt_pool_bytes_of(c->cap, S.maxDocs);
+    return c->delta_req ? mt_delta_size(c, c->delta_req) : MT_OK;
+}
+static int mt_occupancy(mt_ctx* c, uint32_t n, const uint32_t* docs, std::vector<MtOcc>& occ, uint32_t* epoch) {
+    int rc;
+    if ((rc = mtb_sync(c))) return rc;
+    if ((rc = mtb_ensure(c, c->b_tmp0, 4ull * n))) return rc;
+    if ((rc = mtb_ensure(c, c->b_tmp2, sizeof(MtOcc) * n))) return rc;
+    mtb_h2d(c, c->b_tmp0.p, docs, 4ull * n);
+    *epoch = ++c->stage_epoch;
+    if ((rc = mtb_launch_occupancy(c, (const uint32_t*)c->b_tmp0.p, (MtOcc*)c->b_tmp2.p, n, *epoch))) return rc;
+    if ((rc = mtb_sync(c))) return rc;
+    occ.resize(n);
+    mtb_d2h(c, occ.data(), c->b_tmp2.p, sizeof(MtOcc) * n);
+    return MT_OK;
+}
+// mt_docs_resize: sizing pass, validation, room at the pools' tails (a pool is reallocated
+// first when its tail cannot hold the new slices), the move, then the layout table.  Nothing
+// has changed when it fails.
+static int mt_resize_impl(mt_ctx* c, uint32_t n, const uint32_t* docs, const mt_limits* caps) {
+    if (n == 0) return MT_OK;
+    const size_t D = c->S.maxDocs;
+    {
+        std::vector<uint32_t> seen(docs, docs + n);
+        std::sort(seen.begin(), seen.end());
+        if (seen.back() >= D) { c->err = "doc id out of range"; return MT_E_INVALID; }
+        if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { c->err = "a document is named twice"; return MT_E_INVALID; }
+    }
+    std::vector<MtOcc> occ;
+    uint32_t epoch = 0;
+    int rc = mt_occupancy(c, n, docs, occ, &epoch);
+    if (rc) return rc;
+    std::vector<MtDocLayout> ny(n);
+    MtDocLayout nt = c->tot;
+    uint64_t moved = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const MtDocLayout& y = c->layout_h[docs[i]];
+        const mt_limits& q = caps[i];
+        MtDocLayout& z = ny[i];
+        z.rowCap = q.rows_per_doc ? q.rows_per_doc : y.rowCap; z.blkCap = q.blocks_per_doc ? q.blocks_per_doc : y.blkCap;
+        z.textCap = q.text_per_doc ? q.text_per_doc : y.textCap; z.psetCap = q.propsets_per_doc ? q.propsets_per_doc : y.psetCap;
+        z.heapCap = q.heap_per_doc ? q.heap_per_doc : y.heapCap; z.winCap = q.window_per_doc ? q.window_per_doc : y.winCap;
+        z.midCap = q.markers_per_doc ? q.markers_per_doc : y.midCap;
+        z.regCap = q.register_rows_per_doc ? q.register_rows_per_doc : y.regCap;
+        if (z.rowCap > (1u << 30) || z.textCap > (1u << 30) || z.winCap > (1u << 26) || z.regCap > (1u << 24) ||
+            z.blkCap > (1u << 30) || z.heapCap > (1u << 30) || z.psetCap > (1u << 30) || z.midCap > (1u << 30)) {
+            c->err = "per-document capacity too large"; return MT_E_INVALID;
+        }
+        const MtOcc& o = occ[i];
+        const struct { const char* pool; uint32_t have, cap; } chk[8] = {
+            {"rows", o.rows, z.rowCap}, {"blocks", o.blks, z.blkCap}, {"text", o.text, z.textCap},
+            {"property sets", o.psets, z.psetCap}, {"heap", o.heap, z.heapCap}, {"window", o.win, z.winCap},
+            {"markers", o.mids, z.midCap}, {"register rows", o.regs, z.regCap}};
+        for (const auto& k : chk)
+            if (k.cap < k.have) {
+                char b[160];
+                snprintf(b, sizeof b, "document %u: %s capacity %u is below what it holds (%u)", docs[i], k.pool, k.cap, k.have);
+                c->err = b;
+                return MT_E_INVALID;
+            }
+        // a property arena copied whole (capture armed) must hold the arena as it is
+        if (c->delta_cap) {
+            MtDocHdr h;
+            mtb_d2h(c, &h, c->S.hdr + docs[i], sizeof h);
+            if (h.psetTop > 0 && z.psetCap < (uint32_t)h.psetTop) {
+                char b[160];
+                snprintf(b, sizeof b, "document %u: property sets capacity %u is below its arena (%d; delta capture is armed)",
+                         docs[i], z.psetCap, h.psetTop);
+                c->err = b;
+                return MT_E_INVALID;
+            }
+        }
+        // a pool whose capacity stays keeps its slice; the others get new ones at the tails
+        const MtDocLayout s = mt_slice(z), s0 = mt_slice(y);
+        for (auto f : MT_LY_OFF) {
+            if (s.*f == s0.*f) z.*f = y.*f;
+            else { z.*f = nt.*f; nt.*f += s.*f; }
+        }
+        moved += (z.row != y.row ? sizeof(MtRow) * (uint64_t)o.rows : 0) + (z.blk != y.blk ? sizeof(MtBlk) * (uint64_t)o.blks : 0) +
+                 (z.text != y.text ? 2ull * o.text : 0) + (z.pset != y.pset ? sizeof(MtPSet) * (uint64_t)o.psets : 0) +
+                 (z.heap != y.heap ? sizeof(MtHeapE) * ((uint64_t)o.heap + 1) : 0) + (z.win != y.win ? 4ull * o.win : 0) +
+                 (z.mid != y.mid ? 4ull * std::min(y.midCap, z.midCap) : 0) + (z.regr != y.regr ? 4ull * o.regs : 0);
+    }
+    // room: every pool whose tail would pass its allocation goes to twice its size or more
+    MtDocLayout ncap = c->cap;
+    bool re = false;
+    for (auto f : MT_LY_OFF)
+        if (nt.*f > c->cap.*f) { ncap.*f = std::max(2 * (c->cap.*f), nt.*f); re = true; }
+    if (re) {
+        if (c->grow_budget && mt_pool_bytes_of(ncap, D) > c->grow_budget) {
+            c->err = "growing the pools would pass the budget (mt_set_autogrow max_pool_bytes)";
+            return MT_E_OOM;
+        }
+        std::vector<MtPoolDesc> P = mt_pools(c);
+        std::vector<void*> np(P.size(), nullptr);
+        for (size_t k = 0; k < P.size(); k++) {
+            if (ncap.*(P[k].n) == c->cap.*(P[k].n)) continue;
+            const size_t bytes = P[k].esz * (size_t)(ncap.*(P[k].n));
+            if (mtb_malloc(&np[k], bytes ? bytes : 16) != 0) {
+                for (void* q : np) if (q) mtb_free(q);
+                c->err = std::string("pool reallocation failed: ") + P[k].name;
+                return MT_E_OOM;
+            }
+        }
+        for (size_t k = 0; k < P.size(); k++) {
+            if (!np[k]) continue;
+            const size_t used = P[k].esz * (size_t)(c->tot.*(P[k].n));
+            if (used) mtb_d2d(c, np[k], P[k].p, used);
+            mtb_free(P[k].p);
+            P[k].p = np[k];
+            c->grow_realloc++;
+        }
+        mt_set_pools(c, P);
+        c->cap = ncap;
+        c->pool_bytes = mt_pool_bytes_of(c->cap, D);
+    }
+    if ((rc = mtb_ensure(c, c->b_tmp1, sizeof(MtDocLayout) * n))) return rc;
+    mtb_h2d(c, c->b_tmp1.p, ny.data(), sizeof(MtDocLayout) * n);
+    if ((rc = mtb_launch_relocate(c, (const uint32_t*)c->b_tmp0.p, (const MtDocLayout*)c->b_tmp1.p, n, epoch, c->delta_cap == 0))) return rc;
+    if ((rc = mtb_sync(c))) return rc;
+    for (uint32_t i = 0; i < n; i++) {
+        MtDocLayout& y = c->layout_h[docs[i]];
+        const MtDocLayout s = mt_slice(y);
+        for (auto f : MT_LY_OFF) if (ny[i].*f != y.*f) c->dead.*f += s.*f;
+        y = ny[i];
+    }
+    MtDocLayout* table = (MtDocLayout*)c->S.layout;
+    if ((size_t)n * 8 > D) mtb_h2d(c, table, c->layout_h.data(), sizeof(MtDocLayout) * D);
+    else for (uint32_t i = 0; i < n; i++) mtb_h2d(c, table + docs[i], &c->layout_h[docs[i]], sizeof(MtDocLayout));
+    c->tot = nt;
+    c->grow_reloc += n; c->grow_moved += moved;
+    // (the documents have moved; a capture buffer that cannot follow is reported as such)
+    if ((rc = mt_rederive(c))) { c->err = "the documents were moved, but the delta capture buffers could not be sized for them"; return rc; }
+    return MT_OK;
+}
+int MT_FN(docs_resize)(mt_ctx* c, uint32_t n, const uint32_t* docs, const mt_limits* caps) {
+    if (!c || (n && (!docs || !caps))) return MT_E_INVALID;
+    return mt_resize_impl(c, n, docs, caps);
+}
+int MT_FN(doc_caps)(mt_ctx* c, uint32_t n, const uint32_t* docs, mt_limits* out) {
+    if (!c || (n && (!docs || !out))) return MT_E_INVALID;
+    for (uint32_t i = 0; i < n; i++) {
+        if (docs[i] >= c->S.maxDocs) { c->err = "doc id out of range"; return MT_E_INVALID; }
+        const MtDocLayout& y = c->layout_h[docs[i]];
+        mt_limits& q = out[i];
+        q.max_docs = c->S.maxDocs;
+        q.rows_per_doc = y.rowCap; q.blocks_per_doc = y.blkCap; q.text_per_doc = y.textCap; q.propsets_per_doc = y.psetCap;
+        q.heap_per_doc = y.heapCap; q.window_per_doc = y.winCap; q.markers_per_doc = y.midCap; q.register_rows_per_doc = y.regCap;
+    }
+    return MT_OK;
+}
+int MT_FN(doc_occupancy)(mt_ctx* c, uint32_t n, const uint32_t* docs, mt_limits* out) {
+    if (!c || (n && (!docs || !out))) return MT_E_INVALID;
+    if (n == 0) return MT_OK;
+    for (uint32_t i = 0; i < n; i++) if (docs[i] >= c->S.maxDocs) { c->err = "doc id out of range"; return MT_E_INVALID; }
+    std::vector<MtOcc> occ;
+    uint32_t epoch = 0;
+    int rc = mt_occupancy(c, n, docs, occ, &epoch);
+    if (rc) return rc;
+    for (uint32_t i = 0; i < n; i++) {
+        mt_limits& q = out[i];
+        q.max_docs = c->S.maxDocs;
+        q.rows_per_doc = occ[i].rows; q.blocks_per_doc = occ[i].blks; q.text_per_doc = occ[i].text; q.propsets_per_doc = occ[i].psets;
+        q.heap_per_doc = occ[i].heap; q.window_per_doc = occ[i].win; q.markers_per_doc = occ[i].mids;
+        q.register_rows_per_doc = occ[i].regs;
+    }
+    return MT_OK;
+}
+int MT_FN(set_autogrow)(mt_ctx* c, int on, uint64_t max_pool_bytes) {
+    if (!c) return MT_E_INVALID;
+    c->autogrow = on != 0; c->grow_budget = max_pool_bytes;
+    return MT_OK;
+}
+int MT_FN(grow_stats)(mt_ctx* c, uint64_t out[6]) {
+    if (!c || !out) return MT_E_INVALID;
+    uint64_t dead = 0;
+    {   // vacated slices, in bytes (uid / udelta follow the window)
+        const MtDocLayout& d = c->dead;
+        dead = sizeof(MtRow) * d.row + sizeof(MtBlk) * d.blk + sizeof(MtHeapE) * d.heap + 12ull * d.win + 4ull * d.anc +
+               2ull * d.text + sizeof(MtPSet) * d.pset + 4ull * d.mid + 4ull * d.regr;
+    }
+    const uint64_t used = mt_pool_bytes_of(c->tot, c->S.maxDocs);
+    out[0] = c->grow_reloc; out[1] = c->grow_realloc; out[2] = c->grow_moved; out[3] = used - dead; out[4] = dead;
+    out[5] = c->grow_launches;
+    return MT_OK;
+}
+int MT_FN(last_resume)(mt_ctx* c, uint32_t n, uint32_t* out) {
+    if (!c || (n && !out) || n > c->grow_resume.size()) return MT_E_INVALID;
+    for (uint32_t i = 0; i < n; i++) out[i] = c->grow_resume[i];
     return MT_OK;
 }
 
@@ -337,7 +605,10 @@ int MT_FN(set_props)(mt_ctx* c, const mt_prop_table* P) {
     {
         std::vector<uint16_t> ks(c->h_set_key);
         std::sort(ks.begin(), ks.end());
-        const bool wide = (size_t)(std::unique(ks.begin(), ks.end()) - ks.begin()) > MT_WAVE;
+        const size_t nkeys = (size_t)(std::unique(ks.begin(), ks.end()) - ks.begin());
+        const bool wide = nkeys > MT_WAVE;
+        c->prop_nkeys = (uint32_t)nkeys; c->prop_maxset = 0;
+        for (uint32_t i = 0; i < P->n_sets; i++) c->prop_maxset = std::max(c->prop_maxset, P->set_off[i + 1] - P->set_off[i]);
         // Below MT_WAVE keys in all no document can outgrow the lanes, and batches are not
         // scanned (mt_scan_wide); when the table first passes them, the documents open now
         // have keys nobody counted: they replay in the FULL kernels until reopened.
@@ -608,42 +879,69 @@ int MT_FN(apply_batch_parts)(mt_ctx* c, uint32_t n_parts, const mt_op_batch* par
     if (rc) return rc;
     return MT_FN(replay_resident)(c);
 }
-// A capture batch (mt_delta_capture armed): each launch appends records until a document
-// has no headroom left for its next message (MtEngT::dReserve); that run stops there, the
-// records and pasted text so far move to the host, and the next launch resumes the stopped
-// runs (ops.start).  The host copies keep op order per document, so one stable sort by op
-// index restores callback order (mt_delta_records).
+// The stop-and-resume loop of capture batches (mt_delta_capture armed) and growing batches
+// (mt_set_autogrow armed), or both at once.
+// Capture: each launch appends records until a document has no headroom left for its next
+// message (MtEngT::dReserve); that run stops there, the records and pasted text so far move to
+// the host, and the next launch resumes the stopped runs (ops.start).  The host copies keep op
+// order per document, so one stable sort by op index restores callback order (mt_delta_records).
+// Growth: a run stops before an op record its document's pools could not hold
+// (MtEngT::growShort) and leaves the capacities that op needs; the documents are relocated
+// into larger slices (each short pool to max(need, twice its capacity)) and resumed.
+static int mt_resize_impl(mt_ctx* c, uint32_t n, const uint32_t* docs, const mt_limits* caps);
+static uint32_t mt_grow_pch(const mt_ctx* c) {
+    // chunks one new map can take: a map holds at most every key of the table; maps built past
+    // a wave's lanes (applyPropSetWide) reserve room for the old map's keys plus the op set's
+    const uint32_t K = c->prop_nkeys, M = c->prop_maxset;
+    const uint32_t room = K + M <= MT_WAVE ? K : (K + M < MT_PKEYS ? K + M : MT_PKEYS);
+    return room > MT_PSK ? (room + MT_PSK - 1) / MT_PSK : 1;
+}
 static int mt_replay_capture(mt_ctx* c, const MtGen& g) {
     const uint32_t R = c->n_runs;
+    const bool cap = c->delta_cap != 0, grow = c->autogrow && !g.enabled;
+    const size_t gbase = mt_grow_base(R);
     int rc;
-    if ((rc = mtb_ensure(c, c->b_resume, 4ull * R + 4))) return rc;
+    if ((rc = mtb_ensure(c, c->b_resume, 4ull * (gbase + (grow ? (size_t)MT_GROW_N * R : 0)) + 4))) return rc;
     if ((rc = mtb_ensure(c, c->b_start, 4ull * R + 4))) return rc;
-    std::vector<uint32_t> off(R + 1), resume(R), start(R);
+    std::vector<uint32_t> off(R + 1), resume(R), start(R), need, docs, grownAt(R, 0xFFFFFFFFu);
     if (c->run_off.size() == R + 1) off = c->run_off;
     else mtb_d2h(c, off.data(), c->ops.op_off, 4ull * (R + 1));
     for (uint32_t r = 0; r < R; r++) start[r] = off[r];
     c->delta_host.clear(); c->delta_text.clear(); c->delta_over = false; c->delta_launches = 0;
+    c->grow_launches = 0;
     MtOps& o = c->ops;
-    o.drec = (MtDeltaRec*)c->b_drec.p; o.dcount = (unsigned long long*)c->b_dcount.p; o.dcap = c->delta_cap;
-    o.dtext = (uint16_t*)c->b_dtext.p; o.dtcap = c->delta_tcap; o.resume = (uint32_t*)c->b_resume.p;
+    o.resume = (uint32_t*)c->b_resume.p;
     o.start = nullptr;
+    o.grow_pch = grow ? mt_grow_pch(c) : 0;
+    // the growth test lives in the FULL kernels only: an armed batch replays there, as a batch
+    // holding register ops does
+    const bool reg0 = c->batch_reg;
+    if (grow) c->batch_reg = true;
+    const std::vector<uint32_t> zeros(grow ? (size_t)MT_GROW_N * R : 0, 0u);
     for (;;) {
-        const unsigned long long zero[4] = {0, 0, 0, 0};
-        mtb_h2d(c, c->b_dcount.p, zero, sizeof zero);
+        if (cap) {   // (the buffers may have been sized again by a relocation)
+            o.drec = (MtDeltaRec*)c->b_drec.p; o.dcount = (unsigned long long*)c->b_dcount.p; o.dcap = c->delta_cap;
+            o.dtext = (uint16_t*)c->b_dtext.p; o.dtcap = c->delta_tcap;
+            const unsigned long long zero[4] = {0, 0, 0, 0};
+            mtb_h2d(c, c->b_dcount.p, zero, sizeof zero);
+        } else { o.drec = nullptr; o.dcount = nullptr; o.dcap = 0; o.dtext = nullptr; o.dtcap = 0; }
+        if (grow && R) mtb_h2d(c, o.resume + gbase, zeros.data(), 4ull * zeros.size());
         if ((rc = mtb_launch_replay(c, g, R))) break;
         if ((rc = mtb_sync(c))) break;
-        c->delta_launches++;
-        unsigned long long cnt[4];
-        mtb_d2h(c, cnt, c->b_dcount.p, sizeof cnt);
-        if (cnt[MT_DC_REC] > c->delta_cap || cnt[MT_DC_TXT] > c->delta_tcap) { c->delta_over = true; break; }
-        const size_t r0 = c->delta_host.size(), t0 = c->delta_text.size();
-        c->delta_host.resize(r0 + cnt[MT_DC_REC]);
-        if (cnt[MT_DC_REC]) mtb_d2h(c, c->delta_host.data() + r0, c->b_drec.p, sizeof(MtDeltaRec) * cnt[MT_DC_REC]);
-        c->delta_text.resize(t0 + cnt[MT_DC_TXT]);
-        if (cnt[MT_DC_TXT]) mtb_d2h(c, c->delta_text.data() + t0, c->b_dtext.p, 2ull * cnt[MT_DC_TXT]);
-        for (size_t i = r0; i < c->delta_host.size(); i++) {      // pasted text offsets: into the batch's arena
-            MtDeltaRec& q = c->delta_host[i];
-            if (q.kind == MT_DK_INSERT && q.b == 0 && q.pad >= 0) q.pad += (int)t0;
+        c->delta_launches++; c->grow_launches++;
+        if (cap) {
+            unsigned long long cnt[4];
+            mtb_d2h(c, cnt, c->b_dcount.p, sizeof cnt);
+            if (cnt[MT_DC_REC] > c->delta_cap || cnt[MT_DC_TXT] > c->delta_tcap) { c->delta_over = true; break; }
+            const size_t r0 = c->delta_host.size(), t0 = c->delta_text.size();
+            c->delta_host.resize(r0 + cnt[MT_DC_REC]);
+            if (cnt[MT_DC_REC]) mtb_d2h(c, c->delta_host.data() + r0, c->b_drec.p, sizeof(MtDeltaRec) * cnt[MT_DC_REC]);
+            c->delta_text.resize(t0 + cnt[MT_DC_TXT]);
+            if (cnt[MT_DC_TXT]) mtb_d2h(c, c->delta_text.data() + t0, c->b_dtext.p, 2ull * cnt[MT_DC_TXT]);
+            for (size_t i = r0; i < c->delta_host.size(); i++) {      // pasted text offsets: into the batch's arena
+                MtDeltaRec& q = c->delta_host[i];
+                if (q.kind == MT_DK_INSERT && q.b == 0 && q.pad >= 0) q.pad += (int)t0;
+            }
         }
         mtb_d2h(c, resume.data(), c->b_resume.p, 4ull * R);
         bool done = true, progress = false;
@@ -652,12 +950,53 @@ static int mt_replay_capture(mt_ctx* c, const MtGen& g) {
             if (resume[r] != start[r]) progress = true;
         }
         if (done) break;
+        if (grow) {
+            need.resize((size_t)MT_GROW_N * R);
+            mtb_d2h(c, need.data(), o.resume + gbase, 4ull * need.size());
+            if (docs.empty()) { docs.resize(R); mtb_d2h(c, docs.data(), o.doc_ids, 4ull * R); }
+            std::vector<uint32_t> ids; std::vector<mt_limits> want;
+            bool stuck = false;
+            for (uint32_t r = 0; r < R; r++) {
+                const uint32_t* nd = &need[(size_t)MT_GROW_N * r];
+                if (resume[r] >= off[r + 1] || !nd[MT_GROW_MASK]) continue;
+                if (grownAt[r] == resume[r]) { stuck = true; break; }      // grown to what it asked for, and short again
+                grownAt[r] = resume[r];
+                const MtDocLayout& y = c->layout_h[docs[r]];
+                auto up = [](uint32_t nd1, uint32_t cur) -> uint32_t {
+                    if (!nd1) return 0u;
+                    const uint64_t twice = 2ull * cur;
+                    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(nd1, twice), 0x7FFFFFFFull);
+                };
+                mt_limits q{};
+                q.rows_per_doc = up(nd[MT_GROW_ROWS], y.rowCap); q.blocks_per_doc = up(nd[MT_GROW_BLKS], y.blkCap);
+                q.heap_per_doc = up(nd[MT_GROW_HEAP], y.heapCap); q.window_per_doc = up(nd[MT_GROW_WIN], y.winCap);
+                q.text_per_doc = up(nd[MT_GROW_TEXT], y.textCap); q.propsets_per_doc = up(nd[MT_GROW_PSET], y.psetCap);
+                size_t at = 0;
+                while (at < ids.size() && ids[at] != docs[r]) at++;
+                if (at == ids.size()) { ids.push_back(docs[r]); want.push_back(q); }
+                else {   // (two runs of one document: the larger of each)
+                    mt_limits& w = want[at];
+                    w.rows_per_doc = std::max(w.rows_per_doc, q.rows_per_doc); w.blocks_per_doc = std::max(w.blocks_per_doc, q.blocks_per_doc);
+                    w.heap_per_doc = std::max(w.heap_per_doc, q.heap_per_doc); w.window_per_doc = std::max(w.window_per_doc, q.window_per_doc);
+                    w.text_per_doc = std::max(w.text_per_doc, q.text_per_doc); w.propsets_per_doc = std::max(w.propsets_per_doc, q.propsets_per_doc);
+                }
+            }
+            if (stuck) { c->err = "a document grown to what its next op asked for is short again"; rc = MT_E_OOM; break; }
+            if (!ids.empty()) {
+                rc = mt_resize_impl(c, (uint32_t)ids.size(), ids.data(), want.data());
+                if (rc == MT_E_INVALID) rc = MT_E_OOM;                      // a capacity past the pools' limits
+                if (rc) break;
+                progress = true;
+            }
+        }
         if (!progress) { c->err = "delta capture capacity below one message's bound"; rc = MT_E_OOM; break; }
         start = resume;
         mtb_h2d(c, c->b_start.p, start.data(), 4ull * R);
         o.start = (const uint32_t*)c->b_start.p;
     }
-    o.start = nullptr; o.resume = nullptr;
+    o.start = nullptr; o.resume = nullptr; o.grow_pch = 0;
+    c->batch_reg = reg0;
+    if (grow) c->grow_resume = resume;
     c->delta_valid = false;
     return rc;
 }
@@ -667,9 +1006,9 @@ int MT_FN(replay_resident)(mt_ctx* c) {
     if (rc) return rc;
     MtGen g{}; g.enabled = 0;
     c->delta_valid = false;
-    if (c->delta_cap) return mt_replay_capture(c, g);
+    if (c->delta_cap || c->autogrow) return mt_replay_capture(c, g);
     c->ops.drec = nullptr; c->ops.dcount = nullptr; c->ops.dcap = 0; c->ops.dtext = nullptr; c->ops.dtcap = 0;
-    c->ops.resume = nullptr; c->ops.start = nullptr;
+    c->ops.resume = nullptr; c->ops.start = nullptr; c->ops.grow_pch = 0;
     return mtb_launch_replay(c, g, c->n_runs);
 }
 int MT_FN(apply_batch)(mt_ctx* c, const mt_op_batch* B) {
@@ -779,9 +1118,15 @@ int MT_FN(load_snapshot)(mt_ctx* c, const mt_load_batch* B) {
     L.plan_off = (const uint32_t*)c->b_ld_poff.p; L.plan = (const MtLoadStep*)c->b_ld_plan.p;
     return mtb_launch_load(c, L, n);
 }
+static int mt_delta_size(mt_ctx* c, uint64_t capacity);
 int MT_FN(delta_capture)(mt_ctx* c, uint64_t capacity) {
     if (!c) return MT_E_INVALID;
-    c->delta_cap = 0; c->delta_tcap = 0;
+    return mt_delta_size(c, capacity);
+}
+// The capture buffers for `capacity` records, no smaller than the largest document's message
+// bound (sized again when a document's capacities change: mt_rederive).
+static int mt_delta_size(mt_ctx* c, uint64_t capacity) {
+    c->delta_cap = 0; c->delta_tcap = 0; c->delta_req = capacity;
     if (capacity) {
         // one message of the largest document must fit a launch: its range (<= rowCap
         // records) plus the fixed slack; a paste's text is <= the document's text capacity

@@ -354,6 +354,13 @@ struct MtOps {                                // device copy of an mt_op_batch
     uint32_t* resume;                         // capture: op index each run stopped at (op_off[run+1]: done)
     const uint32_t* start;                    // capture resume: first op of each run (null: op_off)
     uint32_t n_runs;
+    // Growth headroom (mt_set_autogrow, FULL kernels; 0 = off): the chunks one new property
+    // map can take (from the property table's key counts).  When set, run r's growth record
+    // follows the resume entries, at mt_grow_rec(ops, r): the minimum capacity of each pool
+    // that fell short before the op the run stopped at (MT_GROW_* order, 0: that pool
+    // sufficed) and, last, the mask of those pools.  (The field fills the padding that
+    // followed n_runs: the struct, a kernel argument of every replay kernel, keeps its layout.)
+    uint32_t grow_pch;
     uint64_t payload_units;                   // records are bounds-checked against it on the device
     // Per-run payload bases in units (null: payload_off is absolute).  An exchanged batch of a
     // million documents holds more than 2^32 payload units; its records' payload_off is then
@@ -361,6 +368,11 @@ struct MtOps {                                // device copy of an mt_op_batch
     const unsigned long long* pay_base;
 };
 enum { MT_DC_REC = 0, MT_DC_RECRES = 1, MT_DC_TXT = 2, MT_DC_TXTRES = 3 };
+enum { MT_GROW_ROWS = 0, MT_GROW_BLKS, MT_GROW_HEAP, MT_GROW_WIN, MT_GROW_TEXT, MT_GROW_PSET, MT_GROW_MASK = 7, MT_GROW_N = 8 };
+MT_INLINE size_t mt_grow_base(uint32_t n_runs) { return ((size_t)n_runs + 3u) & ~(size_t)3u; }    // in resume[] entries
+MT_INLINE uint32_t* mt_grow_rec(const MtOps& ops, uint32_t run) {
+    return ops.resume + mt_grow_base(ops.n_runs) + (size_t)MT_GROW_N * run;
+}
 // Records one message can emit at most, beyond its own range or paste: 2 ensureIntervalBoundary
 // SPLITs and two zamboni calls (the op's and setMinSeq's),
 // each popping <= 2 heap entries that scour one leaf block (8) and may packParent its
@@ -1065,6 +1077,77 @@ template <int RES, bool FULL = true> struct MtEngT {
                                    height + 3 <= MT_L_H;
         return (lRows - rowTop + rfN) >= 4 + k && (lBlks - blkTop + blkFreeN) >= 6 * (height + 2) + 8 + kb &&
                (lHeap - heapN) >= 4 + k && height + 3 <= MT_L_H;
+    }
+    // Text units textGC would keep: linked rows and register clones, markers apart (clones and
+    // pasted rows share slices that a compaction copies once each, so this can pass textTop).
+    MT_HD int textLive() const {
+        int t = 0;
+        for (int base = 0; base < rowTop; base += MT_WAVE) {
+            const int m = (rowTop - base) < MT_WAVE ? (rowTop - base) : MT_WAVE;
+            t += wave_sum(wave_map(m, [&](int k) MT_LAM {
+                const int s = base + k;
+                const uint32_t mt = row(s).meta;
+                const int ln = row(s).len;
+                return (((row(s).parent >= 0) | ((mt & MT_M_REG) != 0)) & !(mt & MT_M_MARKER)) ? ln : 0;
+            }));
+        }
+        return t;
+    }
+    // Growth headroom (mt_set_autogrow): can the op record (ty, fl, p1, p2, plen),
+    // with the end-of-message zamboni it may trigger, run within the document's HBM capacities
+    // (under LDS residency the saved g*Cap, which the LDS caps stand in for)?  k: a paste's
+    // clones; pch: the chunks one new property map can take.  Returns the mask of the pools
+    // that fall short (bit MT_GROW_*) and writes need[MT_GROW_*] for those: the least capacity
+    // under which this test passes.  A pure function of the document's state and capacities;
+    // sound, not tight.  Per op:
+    //   rows    2 boundary splits + 1 new row (+ k), a CUT / COPY one clone per touched row;
+    //           recycled rows count as free
+    //   blocks  ldsHeadroom's 2 * height + MT_B_SLACK (+ ceil(k / 3) + 1); the free list counts
+    //   heap    4 + k, and one entry per leaf block a range op touches (<= its touched rows)
+    //   window  every row the op touches: 3 + k, and a range op's touched rows
+    //   text    every allocation of the message (the payload, merge runs) compacts before it
+    //           fails and is then exactly sized: at most live + payload units beside as many;
+    //           a CUT / COPY first doubles what a compaction keeps (its clones): 2 * live
+    //   psets   one new map per touched row (an insert: one), of pch chunks
+    // touched rows of a range op: one per unit of the range (each is visible in it), at most
+    // every row, plus the two split halves.
+    MT_HD uint32_t growShort(int ty, uint32_t fl, int p1, int p2, int plen, int k, int pch, uint32_t* need) {
+        const bool range = ty == MT_OP_REMOVE || ty == MT_OP_ANNOTATE || ty == MT_OP_CUT || ty == MT_OP_COPY;
+        uint32_t t = 0;                                          // touched rows (<= rowTop + 2)
+        if (range) {
+            int d = (fl & (MT_OPF_REL1 | MT_OPF_REL2)) ? rowTop : (p2 > p1 ? (int)((unsigned)p2 - (unsigned)p1) : 0);
+            if (d < 0 || d > rowTop) d = rowTop;
+            t = (uint32_t)d + 2u;
+        }
+        const uint32_t ku = k > 0 ? (uint32_t)k : 0u;
+        const uint32_t kb = ku ? (ku + 2u) / 3u + 1u : 0u;
+        const bool clone = ty == MT_OP_CUT || ty == MT_OP_COPY;
+        const uint32_t pay = (ty == MT_OP_INSERT && !(fl & MT_OPF_MARKER)) ? (uint32_t)plen : 0u;
+        // every term is below 2^31 (the capacities' limits), every sum below 2^32
+        const uint32_t nRow = (uint32_t)(rowTop - rfN) + 3u + ku + (clone ? t : 0u);
+        const uint32_t nBlk = (uint32_t)(blkTop - blkFreeN) + 2u * (uint32_t)height + (uint32_t)MT_B_SLACK + kb;
+        const uint32_t nHeap = (uint32_t)heapN + 4u + ku + t;
+        const uint32_t nWin = (uint32_t)winN + 3u + ku + t;
+        const uint32_t nProp = ty == MT_OP_ANNOTATE ? t : ((ty == MT_OP_INSERT && (fl & MT_OPF_SEG_PROPS)) ? 1u : 0u);
+        const unsigned long long nPset64 = (unsigned long long)(uint32_t)psetTop + (unsigned long long)nProp * (uint32_t)pch;
+        const uint32_t nPset = nPset64 > 0x7FFFFFFFull ? 0x7FFFFFFFu : (uint32_t)nPset64;
+        const uint32_t live = (uint32_t)textLive();
+        // a CUT / COPY clones whole segments that share the originals' slices; a compaction copies
+        // each clone's text separately, so the op can add up to `live` units without allocating
+        const uint32_t grown = clone ? 2u * live : live + pay;
+        const uint32_t nText = live > 0x1FFF0000u ? 0x7FFFFFFFu : 2u * grown;
+        const uint32_t cRow = kLds ? gRowCap : S.rowCap, cBlk = kLds ? gBlkCap : blkCap, cHeap = kLds ? gHeapCap : S.heapCap,
+                       cWin = kLds ? gWinCap : S.winCap;
+        const uint32_t m = (nRow > cRow ? 1u << MT_GROW_ROWS : 0u) | (nBlk > cBlk ? 1u << MT_GROW_BLKS : 0u) |
+                           (nHeap > cHeap ? 1u << MT_GROW_HEAP : 0u) | (nWin > cWin ? 1u << MT_GROW_WIN : 0u) |
+                           (nText > S.textCap ? 1u << MT_GROW_TEXT : 0u) | (nPset > S.psetCap ? 1u << MT_GROW_PSET : 0u);
+        if (m)
+            wave_for(MT_GROW_N, [&](int q) MT_LAM {
+                const uint32_t v = q == MT_GROW_ROWS ? nRow : q == MT_GROW_BLKS ? nBlk : q == MT_GROW_HEAP ? nHeap : q == MT_GROW_WIN ? nWin
+                                   : q == MT_GROW_TEXT ? nText : q == MT_GROW_PSET ? nPset : 0u;
+                need[q] = q == MT_GROW_MASK ? m : (((m >> q) & 1u) ? v : 0u);
+            });
+        return m;
     }
     MT_HD void ancPut(int u, int h, int a) {
         if constexpr (LDS) mt_lds().uanc[u * MT_L_H + h] = (uint8_t)(a < 0 ? 255 : a);

@@ -20,6 +20,23 @@ struct mt_ctx {
     void *ck_rows = nullptr, *ck_blk = nullptr, *ck_heap = nullptr, *ck_win = nullptr, *ck_text = nullptr,
          *ck_pset = nullptr, *ck_hdr = nullptr, *ck_hold = nullptr, *ck_ovx = nullptr, *ck_mid = nullptr, *ck_reg = nullptr, *ck_regr = nullptr;
     bool ck_valid = false;
+    // Growth (mt_docs_resize / mt_set_autogrow).  The per-document pools are allocated for
+    // `cap` elements, of which `tot` are handed out: a relocated document's new slices go at
+    // the tail (tot), a pool whose tail cannot hold them is reallocated at twice its size or
+    // more; the vacated slices are dead (not reused).  The checkpoint keeps the layout, the
+    // tails and the derived maxima beside the pools' shadows (a shadow is a prefix of a pool
+    // reallocated since).
+    MtDocLayout cap{};
+    std::vector<MtDocLayout> ck_layout;
+    MtDocLayout ck_tot{}, ck_dead{};
+    size_t ck_bytes[12] = {0};                     // allocated bytes of each shadow (mt_ck_parts order)
+    MtDocLayout dead{};                            // vacated elements per pool
+    bool autogrow = false; uint64_t grow_budget = 0;
+    uint64_t grow_reloc = 0, grow_realloc = 0, grow_moved = 0;
+    uint32_t grow_launches = 0;
+    std::vector<uint32_t> grow_resume;             // where each run of the last armed batch stands (mt_last_resume)
+    uint32_t prop_nkeys = 0, prop_maxset = 0;      // the property table's distinct keys and largest set (mt_set_props)
+    uint64_t delta_req = 0;                        // the capacity mt_delta_capture was asked for
     std::unordered_map<uint32_t, std::vector<std::string>> doc_clients;   // mt_set_doc_client_names
     std::string err;
     // device op batch (resident)

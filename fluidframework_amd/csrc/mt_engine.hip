@@ -79,6 +79,23 @@ __global__ __launch_bounds__(64) void mt_pack_kernel(MtState S, const uint32_t* 
     mt_pack_doc(e, stage + off[blockIdx.x], epoch);
 }
 
+// Relocation (mt_docs_resize, mt_pack.h): the sizing pass, then the move of each document
+// into its new slices; one wave per document.
+__global__ __launch_bounds__(64) void mt_occupancy_kernel(MtState S, const uint32_t* docs, MtOcc* out, uint32_t epoch) {
+    __shared__ MtScratch sc;
+    MtEng e;
+    e.bind(S, docs[blockIdx.x], &sc);
+    const MtOcc z = mt_doc_occupancy(e, epoch);
+    if (__lane_id() == 0) out[blockIdx.x] = z;
+}
+__global__ __launch_bounds__(64) void mt_relocate_kernel(MtState S, const uint32_t* docs, const MtDocLayout* ny, uint32_t epoch,
+                                                         int compact) {
+    __shared__ MtScratch sc;
+    MtEng e;
+    e.bind(S, docs[blockIdx.x], &sc);
+    mt_relocate_doc(e, S, ny[blockIdx.x], epoch, compact != 0);
+}
+
 // Document exchange rows (mt_shard.h): one wave per document run.
 __global__ __launch_bounds__(64) void mt_rows_kernel(MtOps ops, int pack, uint32_t first, uint32_t L, const uint64_t* dst,
                                                      unsigned long long* rows, uint64_t* cs) {
@@ -339,6 +356,19 @@ static int mtb_launch_pack(mt_ctx* c, const uint32_t* docs, const uint64_t* off,
     if (!n) return MT_OK;
     (void)hipGetLastError();
     hipLaunchKernelGGL(mt_pack_kernel, dim3(n), dim3(64), 0, (hipStream_t)c->stream, c->S, docs, off, stage, epoch);
+    return mtb_check(c);
+}
+#define MTB_HAVE_RELOCATE 1
+static int mtb_launch_occupancy(mt_ctx* c, const uint32_t* docs, MtOcc* out, uint32_t n, uint32_t epoch) {
+    if (!n) return MT_OK;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(mt_occupancy_kernel, dim3(n), dim3(64), 0, (hipStream_t)c->stream, c->S, docs, out, epoch);
+    return mtb_check(c);
+}
+static int mtb_launch_relocate(mt_ctx* c, const uint32_t* docs, const MtDocLayout* ny, uint32_t n, uint32_t epoch, bool compact) {
+    if (!n) return MT_OK;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(mt_relocate_kernel, dim3(n), dim3(64), 0, (hipStream_t)c->stream, c->S, docs, ny, epoch, compact ? 1 : 0);
     return mtb_check(c);
 }
 

@@ -110,6 +110,21 @@ MT_HD uint32_t mt_replay_run(Eng& e, const MtOps& ops, uint32_t run, uint32_t do
             }
             if (!e.ldsHeadroom(k)) return i;
         }
+        if constexpr (Eng::kFull) {
+            if (!g && ops.grow_pch) {
+                // growth headroom (mt_set_autogrow): the run stops before an op record its pools
+                // could not hold, as a capture run stops for record headroom; the host relocates
+                // the document into larger slices (mt_docs_resize) and resumes it here.  (Read
+                // from the record itself, before the op's operands are live.)
+                const int* rw = (const int*)&ops.rec[i];
+                const uint32_t r0 = (uint32_t)uni(rw[0]), r7 = (uint32_t)uni(rw[7]);
+                const int gty = (int)(r0 & 0xFF);
+                const int gk = gty == MT_OP_PASTE ? e.regCount((int)(r0 >> 16), uni(rw[6])) : 0;
+                if (gty != MT_OP_UNSUPPORTED &&
+                    e.growShort(gty, (r0 >> 8) & 0xFF, uni(rw[4]), uni(rw[5]), (int)(r7 & 0xFFFF), gk, (int)ops.grow_pch,
+                                mt_grow_rec(ops, run))) { e.dStop = 1; return i; }
+            }
+        }
 #if defined(MT_PROFILE) && defined(__HIP_DEVICE_COMPILE__)
         const unsigned long long tg = __builtin_amdgcn_s_memtime();
         if (g) mt_gen_op(e, ops, i, i - o0, nc, *g, rng, lastRef);

@@ -126,7 +126,18 @@ def _bind(lib, prefix: str):
         resolve_remote_position=f("resolve_remote_position", ctypes.c_int, [P, U32, P, P, P, P, P]),
         set_doc_snapshot_chunk=f("set_doc_snapshot_chunk", ctypes.c_int, [P, U32, P, P]),
         reserve_staging=f("reserve_staging", ctypes.c_int, [P, ctypes.c_uint64]),
+        docs_resize=f("docs_resize", ctypes.c_int, [P, U32, P, P]),
+        doc_caps=f("doc_caps", ctypes.c_int, [P, U32, P, P]),
+        doc_occupancy=f("doc_occupancy", ctypes.c_int, [P, U32, P, P]),
+        set_autogrow=f("set_autogrow", ctypes.c_int, [P, ctypes.c_int, ctypes.c_uint64]),
+        grow_stats=f("grow_stats", ctypes.c_int, [P, P]),
+        last_resume=f("last_resume", ctypes.c_int, [P, U32, P]),
     )
+
+
+CAP_FIELDS = tuple(n for n, _ in MtLimits._fields_[1:])          # the per-document capacities of mt_limits
+LIMITS_DTYPE = np.dtype([(n, np.uint32) for n, _ in MtLimits._fields_])
+GROW_STATS = ("relocations", "pool_reallocations", "bytes_moved", "live_bytes", "dead_bytes", "launches")
 
 
 SEG_INFO_FIELDS = ("found", "offset", "obs_pos", "len", "seq", "client", "removed_seq", "removed_client", "prop_set",
@@ -214,7 +225,9 @@ class Engine:
 
     def _check(self, rc: int, what: str):
         if rc != 0:
-            raise MergeTreeError(f"{what} failed ({rc}): {self.fn['last_error'](self.h).decode()}")
+            e = MergeTreeError(f"{what} failed ({rc}): {self.fn['last_error'](self.h).decode()}")
+            e.rc = rc                       # the MT_E_* code
+            raise e
 
     # ---- configuration ----
     def open_docs(self, first: int, n: int):
@@ -409,6 +422,53 @@ class Engine:
         d = _u32(docs)
         out = np.zeros((len(d), 10), np.int32)
         self._check(self.fn["doc_pools"](self.h, len(d), d.ctypes.data, out.ctypes.data), "mt_doc_pools")
+        return out
+
+    # ---- documents that grow (include/mtgpu.h mt_docs_resize / mt_set_autogrow) ----
+    def set_autogrow(self, on: bool = True, max_pool_bytes: int = 0):
+        """mt_set_autogrow: while armed, a document that outgrows a pool is relocated into larger
+        slices and its run resumed (apply / replay_resident are then synchronous);
+        max_pool_bytes > 0 bounds pool_bytes()."""
+        self._check(self.fn["set_autogrow"](self.h, 1 if on else 0, int(max_pool_bytes)), "mt_set_autogrow")
+
+    def resize_docs(self, doc_ids, **caps):
+        """mt_docs_resize: move the documents into new slices with the capacities given as
+        keyword arguments (CAP_FIELDS; a scalar for every document or one value per document;
+        0 or absent keeps the current capacity).  Property-set ids change."""
+        d = _u32(doc_ids)
+        bad = set(caps) - set(CAP_FIELDS)
+        if bad:
+            raise TypeError(f"unknown capacities {sorted(bad)}")
+        arr = np.zeros(len(d), LIMITS_DTYPE)
+        for k, v in caps.items():
+            arr[k] = np.asarray(v, np.uint32)
+        self._check(self.fn["docs_resize"](self.h, len(d), d.ctypes.data, arr.ctypes.data), "mt_docs_resize")
+
+    def _limits_of(self, name: str, doc_ids) -> list[dict]:
+        d = _u32(doc_ids)
+        arr = np.zeros(len(d), LIMITS_DTYPE)
+        self._check(self.fn[name](self.h, len(d), d.ctypes.data, arr.ctypes.data), "mt_" + name)
+        return [{k: int(r[k]) for k in CAP_FIELDS} for r in arr]
+
+    def doc_caps(self, doc_ids) -> list[dict]:
+        """mt_doc_caps: each document's capacities, keyed as resize_docs takes them."""
+        return self._limits_of("doc_caps", doc_ids)
+
+    def doc_occupancy(self, doc_ids) -> list[dict]:
+        """mt_doc_occupancy: what each document holds of every pool (the least capacities
+        resize_docs accepts)."""
+        return self._limits_of("doc_occupancy", doc_ids)
+
+    def grow_stats(self) -> dict:
+        """mt_grow_stats, keyed by GROW_STATS."""
+        out = np.zeros(6, np.uint64)
+        self._check(self.fn["grow_stats"](self.h, out.ctypes.data), "mt_grow_stats")
+        return {k: int(v) for k, v in zip(GROW_STATS, out)}
+
+    def last_resume(self, n_runs: int) -> np.ndarray:
+        """mt_last_resume: the op record each run of the last armed batch stands before."""
+        out = np.zeros(n_runs, np.uint32)
+        self._check(self.fn["last_resume"](self.h, n_runs, out.ctypes.data), "mt_last_resume")
         return out
 
     def load_snapshot(self, batch):
@@ -805,10 +865,16 @@ class MergeTreeClient:
 class ClientGroup:
     """Many MergeTreeClients sharing one engine; flush() packs all queues into one batch."""
 
-    def __init__(self, engine: Engine):
+    def __init__(self, engine: Engine, autogrow: bool = False, max_pool_bytes: int = 0):
+        """autogrow: arm mt_set_autogrow on the engine, so a document that outgrows its pools is
+        given more room instead of failing its flush.  (A relocation changes property-set ids;
+        it happens inside flush(), which bumps `version`: Segment copies handed out before go
+        stale as on any change.)"""
         self.engine = engine
         self.clients: list[MergeTreeClient] = []
         self.version = 0                 # bumped whenever any document changes (Segment copies)
+        if autogrow:
+            engine.set_autogrow(True, max_pool_bytes)
 
     def new_client(self, options: dict | None = None) -> MergeTreeClient:
         d = len(self.clients)

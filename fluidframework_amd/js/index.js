@@ -227,6 +227,27 @@ class Engine {
     loadSnapshot(batch) { this.uploadProps(); addon.loadSnapshot(this.h, batch); }
     sync() { addon.sync(this.h); }
     syncAsync() { return addon.syncAsync(this.h); }
+    /**
+     * Documents that grow (mt_set_autogrow): while armed, a document that outgrows a pool is
+     * relocated into larger slices and its run resumed; maxPoolBytes > 0 bounds the pools.
+     */
+    setAutogrow(on = true, maxPoolBytes = 0) { addon.setAutogrow(this.h, !!on, maxPoolBytes); }
+    /**
+     * mt_docs_resize: caps = {rowsPerDoc, blocksPerDoc, textPerDoc, propsetsPerDoc, heapPerDoc,
+     * windowPerDoc, markersPerDoc, registerRowsPerDoc}, each a number (every document) or one
+     * value per document; absent or 0 keeps the capacity.  Property-set ids change.
+     */
+    resizeDocs(docs, caps = {}) {
+        const c = {};
+        for (const [k, v] of Object.entries(caps)) c[k] = typeof v === "number" ? v : Uint32Array.from(v);
+        addon.resizeDocs(this.h, Uint32Array.from(docs), c);
+    }
+    /** mt_doc_caps: each document's capacities, keyed as resizeDocs takes them. */
+    docCaps(docs) { return addon.docCaps(this.h, Uint32Array.from(docs)); }
+    /** mt_doc_occupancy: what each document holds of every pool (the least capacities resizeDocs accepts). */
+    docOccupancy(docs) { return addon.docOccupancy(this.h, Uint32Array.from(docs)); }
+    /** mt_grow_stats: {relocations, poolReallocations, bytesMoved, liveBytes, deadBytes, launches}. */
+    growStats() { return addon.growStats(this.h); }
     status(docs) { return addon.docStatus(this.h, Uint32Array.from(docs)); }
     getLength(docs, refSeq, client) { return addon.getLength(this.h, Uint32Array.from(docs), Int32Array.from(refSeq), Int32Array.from(client)); }
     /**
@@ -448,7 +469,16 @@ class MergeTreeClient {
 
 /** Many documents on one engine: `newClient()` per document, `flush()` batches. */
 class ClientGroup {
-    constructor(engine) { this.engine = engine; this.clients = []; this.version = 0; }
+    /**
+     * options.autogrow arms mt_set_autogrow on the engine (options.maxPoolBytes bounds it): a
+     * document that outgrows its pools is given more room instead of failing its flush.  A
+     * relocation changes property-set ids; it happens inside flush(), which bumps `version`,
+     * so segments handed out before go stale as on any change.
+     */
+    constructor(engine, options = {}) {
+        this.engine = engine; this.clients = []; this.version = 0;
+        if (options.autogrow) engine.setAutogrow(true, options.maxPoolBytes || 0);
+    }
     newClient(options) {
         const d = this.clients.length;
         if (d >= this.engine.maxDocs) throw new Error("engine document capacity exhausted");

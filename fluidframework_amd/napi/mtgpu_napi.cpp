@@ -632,7 +632,94 @@ napi_value LastError(napi_env env, napi_callback_info info) {
     return s;
 }
 
+// ---- documents that grow (mt_docs_resize / mt_set_autogrow) ----
+const char* const kCapNames[8] = {"rowsPerDoc", "blocksPerDoc", "textPerDoc", "propsetsPerDoc", "heapPerDoc", "windowPerDoc",
+                                  "markersPerDoc", "registerRowsPerDoc"};
+uint32_t* cap_field(mt_limits& L, int k) {
+    uint32_t* f[8] = {&L.rows_per_doc, &L.blocks_per_doc, &L.text_per_doc, &L.propsets_per_doc, &L.heap_per_doc,
+                      &L.window_per_doc, &L.markers_per_doc, &L.register_rows_per_doc};
+    return f[k];
+}
+napi_value limits_array(napi_env env, std::vector<mt_limits>& L) {
+    napi_value out;
+    napi_create_array_with_length(env, L.size(), &out);
+    for (size_t i = 0; i < L.size(); i++) {
+        napi_value o, v;
+        napi_create_object(env, &o);
+        for (int k = 0; k < 8; k++) { napi_create_uint32(env, *cap_field(L[i], k), &v); napi_set_named_property(env, o, kCapNames[k], v); }
+        napi_set_element(env, out, (uint32_t)i, o);
+    }
+    return out;
+}
+// setAutogrow(ctx, on, maxPoolBytes)
+napi_value SetAutogrow(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return nullptr;
+    mt_ctx* c = get_ctx(env, argv[0]); if (!c) return nullptr;
+    bool on = false; napi_get_value_bool(env, argv[1], &on);
+    double b = 0; napi_get_value_double(env, argv[2], &b);
+    int rc = mt_set_autogrow(c, on ? 1 : 0, b > 0 ? (uint64_t)b : 0);
+    return rc ? throw_rc(env, c, rc, "mt_set_autogrow") : undefined(env);
+}
+// resizeDocs(ctx, docs: Uint32Array, caps): caps' members (rowsPerDoc ...) are numbers (every
+// document) or Uint32Arrays (one per document); absent or 0 keeps the capacity
+napi_value ResizeDocs(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return nullptr;
+    mt_ctx* c = get_ctx(env, argv[0]); if (!c) return nullptr;
+    const uint32_t* docs; size_t n;
+    if (!typed(env, argv[1], napi_uint32_array, &docs, &n)) return nullptr;
+    std::vector<mt_limits> L(n);
+    for (int k = 0; k < 8; k++) {
+        bool has = false; napi_has_named_property(env, argv[2], kCapNames[k], &has);
+        if (!has) continue;
+        napi_value v; napi_get_named_property(env, argv[2], kCapNames[k], &v);
+        bool arr = false; napi_is_typedarray(env, v, &arr);
+        if (arr) {
+            const uint32_t* a; size_t m;
+            if (!typed(env, v, napi_uint32_array, &a, &m)) return nullptr;
+            if (m < n) { napi_throw_range_error(env, nullptr, "a capacity array is shorter than docs"); return nullptr; }
+            for (size_t i = 0; i < n; i++) *cap_field(L[i], k) = a[i];
+        } else {
+            uint32_t x = 0; napi_get_value_uint32(env, v, &x);
+            for (size_t i = 0; i < n; i++) *cap_field(L[i], k) = x;
+        }
+    }
+    int rc = mt_docs_resize(c, (uint32_t)n, docs, L.data());
+    return rc ? throw_rc(env, c, rc, "mt_docs_resize") : undefined(env);
+}
+// docCaps(ctx, docs) / docOccupancy(ctx, docs) -> [{rowsPerDoc, ...}]
+static napi_value doc_limits(napi_env env, napi_callback_info info, bool occ) {
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    mt_ctx* c = get_ctx(env, argv[0]); if (!c) return nullptr;
+    const uint32_t* docs; size_t n;
+    if (!typed(env, argv[1], napi_uint32_array, &docs, &n)) return nullptr;
+    std::vector<mt_limits> L(n);
+    int rc = occ ? mt_doc_occupancy(c, (uint32_t)n, docs, L.data()) : mt_doc_caps(c, (uint32_t)n, docs, L.data());
+    return rc ? throw_rc(env, c, rc, occ ? "mt_doc_occupancy" : "mt_doc_caps") : limits_array(env, L);
+}
+napi_value DocCaps(napi_env env, napi_callback_info info) { return doc_limits(env, info, false); }
+napi_value DocOccupancy(napi_env env, napi_callback_info info) { return doc_limits(env, info, true); }
+// growStats(ctx) -> {relocations, poolReallocations, bytesMoved, liveBytes, deadBytes, launches}
+napi_value GrowStats(napi_env env, napi_callback_info info) {
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    mt_ctx* c = get_ctx(env, argv[0]); if (!c) return nullptr;
+    uint64_t s[6];
+    int rc = mt_grow_stats(c, s);
+    if (rc) return throw_rc(env, c, rc, "mt_grow_stats");
+    const char* names[6] = {"relocations", "poolReallocations", "bytesMoved", "liveBytes", "deadBytes", "launches"};
+    napi_value o, v;
+    napi_create_object(env, &o);
+    for (int k = 0; k < 6; k++) { napi_create_double(env, (double)s[k], &v); napi_set_named_property(env, o, names[k], v); }
+    return o;
+}
+
 const napi_property_attributes kAttr = (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable);
+// The growth calls are callable but not enumerated: Object.keys(addon) stays the surface the
+// hosts were written against.
+const napi_property_attributes kQuiet = (napi_property_attributes)(napi_writable | napi_configurable);
 
 napi_value Init(napi_env env, napi_value exports) {
     const napi_property_descriptor props[] = {
@@ -662,6 +749,11 @@ napi_value Init(napi_env env, napi_value exports) {
         {"deltaText", nullptr, DeltaText, nullptr, nullptr, nullptr, kAttr, nullptr},
         {"docPset", nullptr, DocPset, nullptr, nullptr, nullptr, kAttr, nullptr},
         {"lastError", nullptr, LastError, nullptr, nullptr, nullptr, kAttr, nullptr},
+        {"setAutogrow", nullptr, SetAutogrow, nullptr, nullptr, nullptr, kQuiet, nullptr},
+        {"resizeDocs", nullptr, ResizeDocs, nullptr, nullptr, nullptr, kQuiet, nullptr},
+        {"docCaps", nullptr, DocCaps, nullptr, nullptr, nullptr, kQuiet, nullptr},
+        {"docOccupancy", nullptr, DocOccupancy, nullptr, nullptr, nullptr, kQuiet, nullptr},
+        {"growStats", nullptr, GrowStats, nullptr, nullptr, nullptr, kQuiet, nullptr},
     };
     napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
     return exports;

@@ -356,6 +356,71 @@ int  mt_pool_bytes(mt_ctx* ctx, uint64_t* bytes);
  * engine's resume point: replay a stream on the same starting documents). */
 int  mt_checkpoint(mt_ctx* ctx);
 int  mt_restore(mt_ctx* ctx);
+
+/*
+ * Documents that outgrow their pools.  A document's capacities are set when
+ * the context is created; these calls give it more room (or less) afterwards.
+ *
+ * mt_docs_resize moves each named document into new slices of the per-document pools with
+ * the capacities caps[i] (rows_per_doc ... register_rows_per_doc; a field of 0 keeps the
+ * current capacity, max_docs is ignored; capacities may grow or shrink).  A pool whose
+ * capacity stays as it is keeps its slice (nothing of it is copied or compacted); the window's
+ * capacity also sizes the per-op scratch beside it.  The move runs on the
+ * device, one wavefront per document: rows and blocks move by index (row ids, block ids, the
+ * free lists and the recycled-row stack stay valid; delta records and mt_seg_info.row refer
+ * to row ids), the heap, the window, the marker table and the register arena move as they
+ * are, text is compacted as the engine's own text compaction does, and the property maps are
+ * compacted to those that linked rows and register clones still reference, so property-set
+ * ids change (mt_seg_info.prop_set and earlier mt_delta_rec ids go stale) - except while
+ * mt_delta_capture is armed, when the arena is copied as it is and the ids stay valid.  The
+ * documents' text, segments and snapshots are unchanged by the call.
+ * A capacity below what the document holds (mt_doc_occupancy) is rejected: MT_E_INVALID,
+ * mt_last_error names the document and the pool, and nothing has moved (the call is all or
+ * nothing).  New slices go at the tail of each pool; a pool whose tail cannot hold them is
+ * reallocated at twice its size or more (device-to-device copy, the old allocation freed).
+ * MT_E_OOM if that allocation fails or would pass mt_set_autogrow's budget: every document
+ * stays where it was.  Vacated slices are not reused (mt_grow_stats counts them as dead).
+ * mt_pool_bytes, the capture buffers' minimum sizes and everything else derived from the
+ * capacities follow.  mt_checkpoint keeps the layout beside the pools: mt_restore after a
+ * relocation brings back the documents and their capacities as of the checkpoint.
+ * Synchronous.
+ */
+int  mt_docs_resize(mt_ctx* ctx, uint32_t n, const uint32_t* doc_ids, const mt_limits* caps /*[n]*/);
+/* The capacities of each document (max_docs: the context's). */
+int  mt_doc_caps(mt_ctx* ctx, uint32_t n, const uint32_t* doc_ids, mt_limits* out /*[n]*/);
+/* What each document holds of every pool, from a sizing pass on the device, in the capacity
+ * fields of out[i]: the least capacities mt_docs_resize accepts.  Rows and blocks by their
+ * high-water marks (both move by index), live text units (what a text compaction keeps:
+ * linked segments and register clones), chunks of the property maps still referenced, heap
+ * and window entries, the highest marker id a segment carries and the register clone rows. */
+int  mt_doc_occupancy(mt_ctx* ctx, uint32_t n, const uint32_t* doc_ids, mt_limits* out /*[n]*/);
+/*
+ * Growing on demand.  While armed (on != 0; off by default), mt_apply_batch,
+ * mt_apply_batch_parts and mt_replay_resident are synchronous, as under mt_delta_capture, and
+ * run in the kernels that carry the stop / resume code.  Before each op record the replay tests
+ * whether the op, with the end-of-message zamboni it may trigger, fits the document's
+ * capacities (a sound, conservative bound: DESIGN.md §10); a run whose document falls short
+ * stops before that op, the library relocates the document (each short pool to the larger of
+ * what the op needs and twice its capacity, the others kept) and resumes the run, until every
+ * run has finished.  No MT_DS_OOM_ROWS / BLOCKS / TEXT / PROPS / HEAP / WINDOW bit is then set;
+ * results are bit-exact with a replay on ample capacities.  With mt_delta_capture armed as
+ * well, runs stop for either reason and the records come in the same order.
+ * max_pool_bytes > 0 bounds mt_pool_bytes: when growth would pass it (or an allocation
+ * fails) the call returns MT_E_OOM, every document consistent (status 0) before an op record
+ * it had not started: mt_last_resume tells which.
+ * Not grown: the 64 registers and the overlap side list (fixed per document), the register
+ * row arena and the marker table (mt_docs_resize enlarges those when asked).  Stream
+ * generation (mt_generate*) is not covered.  Off: launches select the kernels they always did
+ * and an overflow sets its MT_DS_OOM_* bit.
+ */
+int  mt_set_autogrow(mt_ctx* ctx, int on, uint64_t max_pool_bytes /*0: no budget*/);
+/* out: documents relocated, pool reallocations (both since the context was created), bytes
+ * moved by relocations, bytes of the pools in use by documents, bytes of vacated slices (dead),
+ * replay launches of the last armed batch. */
+int  mt_grow_stats(mt_ctx* ctx, uint64_t out[6]);
+/* Per run of the last batch replayed with mt_set_autogrow armed: the op record it stands
+ * before (== the run's end when it finished). */
+int  mt_last_resume(mt_ctx* ctx, uint32_t n_runs, uint32_t* out);
 void mt_destroy(mt_ctx* ctx);
 const char* mt_last_error(mt_ctx* ctx);
 
