@@ -5,15 +5,19 @@
 // EMU: host memory + host-emulated waves), which exists only so the CPU test
 // suite can exercise the identical engine logic against the oracle.
 //
-// Required from the includer:
+// Required from the includer (c: the context; a launch returns MT_OK or MT_E_HIP):
 //   MT_FN(name)           exported symbol name
-//   mtb_malloc/mtb_free   pool allocation
-//   mtb_h2d/mtb_d2h/mtb_memset, mtb_sync
-//   mtb_launch_replay(ctx, S, ops, gen, n_runs)
-//   mtb_launch_open(ctx, S, first, n)
-//   mtb_launch_update_seq(ctx, S, docs, msn, seq, n)
-//   mtb_launch_get_length(ctx, S, docs, ref, cli, out, n)
-//   mtb_event_start / mtb_event_stop_ms
+//   mtb_init(c), mtb_fini(c), mtb_malloc(&p, bytes), mtb_free(p), mtb_memset(p, v, bytes)
+//   mtb_h2d / mtb_d2h / mtb_d2d(c, dst, src, bytes), mtb_sync(c)
+//   mtb_stage_get(c, bytes), mtb_stage_send(c, dev, bytes), mtb_host_stage(c, bytes, buf)
+//   mtb_cu_count(c); with MTB_HAVE_MASKED_STREAMS, mtb_masked_streams(c): may the plan use MT_LANE_A / B?
+//   mt_plan.h, included after the above; mtb_launch_replay(c, gen, n_runs): the generator, or its plan
+//   mtb_launch_open(c, first, n), mtb_launch_load(c, load, n)
+//   mtb_launch_update_seq(c, docs, msn, seq, n), mtb_launch_get_length(c, docs, ref, cli, out, n)
+//   mtb_launch_query(c, q, groups, out, n_groups), mtb_launch_gather_text(c, at, len, off, dst, n)
+//   mtb_launch_pack_size(c, docs, out, n, epoch), mtb_launch_pack(c, docs, off, stage, n, epoch)
+//   mtb_launch_rows(c, pack, first, n, L, dst, rows, checksums)
+//   with MTB_HAVE_RELOCATE: mtb_launch_occupancy(c, docs, out, n, epoch), mtb_launch_relocate(c, docs, ny, n, epoch, compact)
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -25,118 +29,8 @@
 #include <string>
 #include <vector>
 #include "mt_ctx.h"
+#include "mt_plan.h"
 #include "mt_shard.h"
-
-static int mtb_ensure(mt_ctx* c, mt_ctx::DevBuf& b, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.cap >= bytes) return MT_OK;
-    if (b.p) mtb_free(b.p);
-    b.p = nullptr; b.cap = 0;
-    if (mtb_malloc(&b.p, bytes) != 0) { c->err = "device allocation failed"; return MT_E_OOM; }
-    b.cap = bytes;
-    return MT_OK;
-}
-
-// The run lists of the size classes for the resident batch (host lists uploaded once per
-// batch): long runs (>= big_min_ops op records) in [0, n_long), the rest after them.
-static int mt_size_class_lists(mt_ctx* c) {
-    if (c->runs_gen == c->batch_gen && c->runs_min == c->big_min_ops) return MT_OK;
-    const uint32_t R = c->n_runs;
-    std::vector<uint32_t> lst; lst.reserve(R);
-    for (uint32_t r = 0; r < R && c->run_off.size() == R + 1; r++)
-        if (c->run_off[r + 1] - c->run_off[r] >= c->big_min_ops) lst.push_back(r);
-    c->n_long = (uint32_t)lst.size();
-    for (uint32_t r = 0; r < R && c->run_off.size() == R + 1; r++)
-        if (c->run_off[r + 1] - c->run_off[r] < c->big_min_ops) lst.push_back(r);
-    c->n_short = (uint32_t)lst.size() - c->n_long;
-    int rc;
-    if ((rc = mtb_ensure(c, c->b_runs, 4ull * lst.size() + 4))) return rc;
-    if (!lst.empty()) mtb_h2d(c, c->b_runs.p, lst.data(), 4ull * lst.size());
-    c->runs_gen = c->batch_gen; c->runs_min = c->big_min_ops;
-    return MT_OK;
-}
-
-// The partition rule (mt_plan_partition): a model of the measured kernels.
-// Per-message times of one document's wave, in microseconds: MT_PLAN_T_BLK in the block-
-// residency kernel with 16 documents per CU (config 2: 153.5 ms / 10,000 messages; MT_PLAN_T_LONE
-// alone), the same kernel's long document whose tree outgrows LDS and continues in HBM
-// (MT_PLAN_T_CONT past about MT_PLAN_LDS_FIT messages: config 5's 1,302 ms / 65,521 messages
-// unpartitioned), MT_PLAN_T_WIDE in the wide kernel with MT_PLAN_WIDE_PER_CU documents per CU
-// (LDS-bound: 21.2 KB each; 1,048,576-document config 5 at 256:224, 5,338 ms for 699 M messages
-// on 224 CUs) and MT_PLAN_T_WLONE its lone longest document (config 5: 887.9 ms / 65,521).
-#define MT_PLAN_T_BLK   15.3
-#define MT_PLAN_T_LONE  13.4
-#define MT_PLAN_T_CONT  19.9
-#define MT_PLAN_T_WIDE  12.0
-#define MT_PLAN_WIDE_PER_CU 7
-#define MT_PLAN_T_WLONE 13.5
-#define MT_PLAN_LDS_FIT 10000u
-struct MtPlanSide { double msgs = 0, extra = 0; uint32_t longest = 0; };
-// Step estimate (microseconds) of one kernel on `cus` CUs holding `per_cu` documents each.
-static double mt_plan_side(const MtPlanSide& s, double cus, double per_cu, double t_thr, double t_lone, bool cont) {
-    if (s.msgs == 0) return 0;
-    const double thr = (s.msgs * t_thr + (cont ? s.extra * (MT_PLAN_T_CONT - MT_PLAN_T_BLK) : 0)) / (cus * per_cu);
-    const double lat = cont && s.longest > MT_PLAN_LDS_FIT
-                           ? MT_PLAN_LDS_FIT * t_lone + (double)(s.longest - MT_PLAN_LDS_FIT) * MT_PLAN_T_CONT
-                           : (double)s.longest * t_lone;
-    return thr > lat ? thr : lat;
-}
-static void mt_plan_partition_impl(const uint32_t* len, uint32_t n, uint32_t ncu, uint32_t* min_ops, uint32_t* cus,
-                                   double* est_us) {
-    *min_ops = 0; *cus = 0;
-    std::vector<uint32_t> L(len, len + n);
-    std::sort(L.begin(), L.end(), std::greater<uint32_t>());
-    // suffix sums over the sorted lengths: messages and continuation messages of the runs < m
-    MtPlanSide all;
-    for (uint32_t x : L) { all.msgs += x; all.extra += x > MT_PLAN_LDS_FIT ? x - MT_PLAN_LDS_FIT : 0; }
-    all.longest = n ? L[0] : 0;
-    const double off = mt_plan_side(all, ncu, 16, MT_PLAN_T_BLK, MT_PLAN_T_LONE, true);
-    double best = off, bestSum = 0; uint32_t bm = 0, bk = 0;
-    const uint32_t step = ncu >= 8 ? ncu / 8 : 1;                      // whole XCD shares
-    for (uint32_t m = 256; m <= 32768 && ncu >= 2; m *= 2) {
-        MtPlanSide A, B;
-        for (uint32_t x : L) {
-            MtPlanSide& s = x >= m ? A : B;
-            s.msgs += x; s.extra += x > MT_PLAN_LDS_FIT ? x - MT_PLAN_LDS_FIT : 0;
-            if (x > s.longest) s.longest = x;
-        }
-        if (A.msgs == 0) break;
-        for (uint32_t k = step; k < ncu; k += step) {
-            const double ta = mt_plan_side(A, k, MT_PLAN_WIDE_PER_CU, MT_PLAN_T_WIDE, MT_PLAN_T_WLONE, false);
-            const double tb = mt_plan_side(B, ncu - k, 16, MT_PLAN_T_BLK, MT_PLAN_T_LONE, true);
-            const double t = ta > tb ? ta : tb, sum = ta + tb;
-            // the lowest step; within 1 % of it, the lowest total busy time
-            if (t < best * 0.99 || (t <= best * 1.01 && bm && sum < bestSum)) { best = t < best ? t : best; bestSum = sum; bm = m; bk = k; }
-        }
-    }
-    if (bm && best < off * 0.95) { *min_ops = bm; *cus = bk; if (est_us) *est_us = best; }
-    else if (est_us) *est_us = off;
-}
-// MT_PARTITION_AUTO: the resident batch's partition from its run lengths (once per batch).
-static void mt_auto_partition(mt_ctx* c) {
-    if (!c->part_auto || c->use_lds != 2 || c->auto_gen == c->batch_gen) return;
-    c->auto_gen = c->batch_gen;
-    const uint32_t R = c->n_runs;
-    if (c->run_off.size() != R + 1) { c->big_min_ops = 0; c->part_cus = 0; return; }
-    std::vector<uint32_t> len(R);
-    for (uint32_t r = 0; r < R; r++) len[r] = c->run_off[r + 1] - c->run_off[r];
-    uint32_t m = 0, k = 0;
-    mt_plan_partition_impl(len.data(), R, mtb_cu_count(c), &m, &k, nullptr);
-    c->big_min_ops = m; c->part_cus = m ? k : 0;
-}
-
-// The continuation class of block residency for the resident batch: whether any run has at
-// least cont_min_ops op records (n_cont > 0 launches the kernel with the in-wave continuation).
-static int mt_cont_lists(mt_ctx* c) {
-    if (c->cont_gen == c->batch_gen && c->cont_min_made == c->cont_min_ops) return MT_OK;
-    const uint32_t R = c->n_runs;
-    const bool ok = c->run_off.size() == R + 1;
-    uint32_t nc = 0;
-    for (uint32_t r = 0; r < R && ok; r++) nc += c->run_off[r + 1] - c->run_off[r] >= c->cont_min_ops;
-    c->n_cont = ok ? nc : 0; c->n_nocont = ok ? R - nc : 0;
-    c->cont_gen = c->batch_gen; c->cont_min_made = c->cont_min_ops;
-    return MT_OK;
-}
 
 // Host loops over a batch's ops run on up to 16 threads once a batch is large enough to pay
 // for them (ingest: validation and the SoA -> 32-byte record packing).

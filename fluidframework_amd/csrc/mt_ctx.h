@@ -59,6 +59,8 @@ struct mt_ctx {
     uint32_t n_runs = 0;
     std::vector<uint32_t> run_off;     // host copy of the resident batch's op offsets (n_runs + 1)
     uint64_t batch_gen = 0;            // bumped whenever a batch becomes resident
+    // What follows feeds the replay plan (mt_plan.h mt_plan_replay), which alone decides the
+    // launches of a batch; the streams and events are the HIP backend's lanes for them.
     // Size classes (mt_set_size_class): runs of at least big_min_ops op records replay in the
     // long-document kernel on stream2, concurrently with the block-residency kernel for the
     // rest; the run lists live in b_runs (long runs first), rebuilt per resident batch.
@@ -75,7 +77,7 @@ struct mt_ctx {
     // kernel with the in-wave HBM continuation (a long document that outgrows LDS keeps its head
     // start); other batches in the one without it (no scratch; an outgrown document finishes
     // in a second, all-HBM launch).
-    uint32_t cont_min_ops = 16384, n_cont = 0, n_nocont = 0, cont_min_made = 0;
+    uint32_t cont_min_ops = 16384, n_cont = 0, cont_min_made = 0;
     uint64_t cont_gen = ~0ull;
     void* streamA = nullptr; void* streamB = nullptr; void* ev_joinB = nullptr;
     // mt_apply_batch / mt_upload_batch staging: two pinned host slots used alternately, each

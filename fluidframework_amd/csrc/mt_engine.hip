@@ -188,13 +188,13 @@ static int mtb_check(mt_ctx* c) {
     return MT_OK;
 }
 // The two CU-masked streams of partitioned size classes: A holds part_cus CUs spread evenly
-// over the device (every k-th CU, so every XCD gives its share), B the rest.
-static int mtb_partition_streams(mt_ctx* c) {
-    if (c->part_made == c->part_cus && c->streamA) return 0;
+// over the device (every k-th CU, so every XCD gives its share), B the rest.  False: not to be had.
+static bool mtb_masked_streams(mt_ctx* c) {
+    if (c->part_made == c->part_cus && c->streamA) return true;
     if (c->streamA) { (void)hipStreamSynchronize((hipStream_t)c->streamA); (void)hipStreamDestroy((hipStream_t)c->streamA); c->streamA = nullptr; }
     if (c->streamB) { (void)hipStreamSynchronize((hipStream_t)c->streamB); (void)hipStreamDestroy((hipStream_t)c->streamB); c->streamB = nullptr; }
     int ncu = 0;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || ncu <= 0) return 1;
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || ncu <= 0) return false;
     const uint32_t want = c->part_cus < (uint32_t)ncu ? c->part_cus : (uint32_t)ncu - 1;
     std::vector<uint32_t> ma((ncu + 31) / 32, 0u), mb((ncu + 31) / 32, 0u);
     uint32_t got = 0;
@@ -203,173 +203,100 @@ static int mtb_partition_streams(mt_ctx* c) {
         if (inA) { ma[i / 32] |= 1u << (i % 32); got++; } else mb[i / 32] |= 1u << (i % 32);
     }
     hipStream_t a, b;
-    if (hipExtStreamCreateWithCUMask(&a, (uint32_t)ma.size(), ma.data()) != hipSuccess) return 1;
-    if (hipExtStreamCreateWithCUMask(&b, (uint32_t)mb.size(), mb.data()) != hipSuccess) { (void)hipStreamDestroy(a); return 1; }
+    if (hipExtStreamCreateWithCUMask(&a, (uint32_t)ma.size(), ma.data()) != hipSuccess) return false;
+    if (hipExtStreamCreateWithCUMask(&b, (uint32_t)mb.size(), mb.data()) != hipSuccess) { (void)hipStreamDestroy(a); return false; }
     c->streamA = a; c->streamB = b;
     if (!c->ev_joinB) { hipEvent_t e; (void)hipEventCreateWithFlags(&e, hipEventDisableTiming); c->ev_joinB = e; }
     c->part_made = c->part_cus;
-    return 0;
+    return true;
 }
-static void launch_replay(mt_ctx* c, hipStream_t s, uint32_t n_runs, bool full) {
-    uint32_t* cur = (uint32_t*)c->b_cursor.p;
-    if (c->use_lds == 2 && c->big_min_ops && c->n_long && c->part_cus && !mtb_partition_streams(c)) {
-        // partitioned size classes: long runs on stream A's CUs in the wide block-residency
-        // kernel (~21 KB of LDS, up to 7 per CU), the rest on stream B's CUs; joined.  Capture
-        // batches (FULL): the block-residency kernel, one workgroup per SIMD (each padded to a
-        // quarter of the CU's 160 KB of LDS: any total in (160 KB / 5, 160 KB / 4] leaves four)
-        const uint32_t* runs = (const uint32_t*)c->b_runs.p;
-        hipStream_t sa = (hipStream_t)c->streamA, sb = (hipStream_t)c->streamB;
-        const uint32_t pad = 27u << 10;
-        (void)hipEventRecord((hipEvent_t)c->ev_fork, s);
-        (void)hipStreamWaitEvent(sa, (hipEvent_t)c->ev_fork, 0);
-        (void)hipStreamWaitEvent(sb, (hipEvent_t)c->ev_fork, 0);
-        if (full) mtk_blk_full(sa, c->n_long, c->S, c->ops, runs, cur, c->lds_blks, c->lds_heap, pad);
-        else mtk_blkw(sa, c->n_long, c->S, c->ops, runs, cur);
-        if (c->n_short) {
-            if (full) mtk_blk_full(sb, c->n_short, c->S, c->ops, runs + c->n_long, cur, c->lds_blks, c->lds_heap);
-            else mtk_blk_fast(sb, c->n_short, c->S, c->ops, runs + c->n_long, cur, c->lds_blks, c->lds_heap);
-        }
-        (void)hipEventRecord((hipEvent_t)c->ev_join, sa);
-        (void)hipEventRecord((hipEvent_t)c->ev_joinB, sb);
-        (void)hipStreamWaitEvent(s, (hipEvent_t)c->ev_join, 0);
-        (void)hipStreamWaitEvent(s, (hipEvent_t)c->ev_joinB, 0);
-        if (!full && c->n_short) mtk_hbm(full, s, n_runs, c->S, c->ops, cur);   // documents that outgrew LDS
-        return;
-    }
-    if (c->use_lds == 2 && c->big_min_ops && c->n_long) {
-        // size classes: long runs on stream2 in the wide block-residency kernel (launched first,
-        // so the long runs take their slots before the short ones fill the CUs), the rest here,
-        // joined; capture batches (FULL) take the long-document kernel
-        const uint32_t* runs = (const uint32_t*)c->b_runs.p;
-        hipStream_t s2 = (hipStream_t)c->stream2;
-        (void)hipEventRecord((hipEvent_t)c->ev_fork, s);
-        (void)hipStreamWaitEvent(s2, (hipEvent_t)c->ev_fork, 0);
-        if (full) mtk_big(full, s2, c->n_long, c->S, c->ops, runs, cur, MT_G_WIN, 0, MT_G_HEAP);
-        else mtk_blkw(s2, c->n_long, c->S, c->ops, runs, cur);
-        if (c->n_short) {
-            if (full) mtk_blk_full(s, c->n_short, c->S, c->ops, runs + c->n_long, cur, c->lds_blks, c->lds_heap);
-            else mtk_blk_fast(s, c->n_short, c->S, c->ops, runs + c->n_long, cur, c->lds_blks, c->lds_heap);
-        }
-        (void)hipEventRecord((hipEvent_t)c->ev_join, s2);
-        (void)hipStreamWaitEvent(s, (hipEvent_t)c->ev_join, 0);
-        if (!full && c->n_short) mtk_hbm(full, s, n_runs, c->S, c->ops, cur);   // documents that outgrew LDS
-        return;
-    }
-    if (c->use_lds == 3) mtk_big(full, s, n_runs, c->S, c->ops, nullptr, cur, c->lds_rows, c->lds_blks, c->lds_heap);
-    else if (c->use_lds == 2) {
-        if (full) mtk_blk_full(s, n_runs, c->S, c->ops, nullptr, cur, c->lds_blks, c->lds_heap);   // continues in-wave
-        else if (c->n_cont == 0) {
-            // no run reaches the continuation threshold: the kernel without the second engine
-            mtk_blk_fast(s, n_runs, c->S, c->ops, nullptr, cur, c->lds_blks, c->lds_heap);
-            mtk_hbm(full, s, n_runs, c->S, c->ops, cur);                        // documents that outgrew LDS
-        } else {
-            // a long run is in the batch: one launch of the kernel with the in-wave continuation
-            // (the runs start in batch order, longest first under LPT; two kernels on two streams
-            // let short runs take the slots first and measured slower)
-            mtk_blk_fast_cont(s, n_runs, c->S, c->ops, nullptr, cur, c->lds_blks, c->lds_heap);
-        }
-    } else if (c->use_lds) {
-        mtk_lds(full, s, n_runs, c->S, c->ops, cur, c->lds_rows, c->lds_blks, c->lds_heap);
-        mtk_hbm(full, s, n_runs, c->S, c->ops, cur);
-    } else mtk_hbm(full, s, n_runs, c->S, c->ops, nullptr);
-}
-static int mt_size_class_lists(mt_ctx* c);
-static int mt_cont_lists(mt_ctx* c);
-static void mt_auto_partition(mt_ctx* c);
 static uint32_t mtb_cu_count(mt_ctx* c) {
     int ncu = 0;
     return hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && ncu > 0 ? (uint32_t)ncu : 256u;
 }
+#define MTB_HAVE_MASKED_STREAMS 1
+#include "mt_plan.h"
+
+// The generator's launch, or the plan's (mt_plan.h): a lane other than MAIN waits for the fork event recorded on the
+// main stream before its first launch; the main stream waits for every lane in use before REST and after the last launch.
 static int mtb_launch_replay(mt_ctx* c, const MtGen& g, uint32_t n_runs) {
     if (n_runs == 0) return MT_OK;
-    if (!g.enabled) mt_auto_partition(c);
-    if (!g.enabled && c->use_lds == 2 && !c->big_min_ops) {
-        int rc = mt_cont_lists(c);
-        if (rc) return rc;
-    }
     hipStream_t s = (hipStream_t)c->stream;
-    if (!g.enabled && c->use_lds == 2 && c->big_min_ops) {
-        int rc = mt_size_class_lists(c);
-        if (rc) return rc;
-    }
     (void)hipGetLastError();
+    MtPlan P{};
+    if (int rc = g.enabled ? MT_OK : mt_plan_replay(c, mt_replay_full(c), P)) return rc;
     (void)hipEventRecord((hipEvent_t)c->ev0, s);
     if (g.enabled) mtk_generate(s, n_runs, c->S, c->ops, g);
-    else launch_replay(c, s, n_runs, c->ops.drec || c->batch_reg || c->batch_wide);
+    uint32_t* cur = (uint32_t*)c->b_cursor.p;
+    const hipStream_t lane[MT_LANE_N] = {s, (hipStream_t)c->stream2, (hipStream_t)c->streamA, (hipStream_t)c->streamB};
+    const hipEvent_t done[MT_LANE_N] = {nullptr, (hipEvent_t)c->ev_join, (hipEvent_t)c->ev_join, (hipEvent_t)c->ev_joinB};
+    unsigned open = 0;                     // the lanes the main stream has yet to wait for
+    auto join = [&] {
+        for (int k = 1; k < MT_LANE_N; k++) if (open >> k & 1) { (void)hipEventRecord(done[k], lane[k]); (void)hipStreamWaitEvent(s, done[k], 0); }
+        open = 0;
+    };
+    for (int i = 0; i < P.n; i++) {
+        const MtLaunch& L = P.l[i];
+        const hipStream_t q = lane[L.lane];
+        if (L.kernel == MT_PK_REST) join();
+        if (L.lane != MT_LANE_MAIN && !(open >> L.lane & 1)) {
+            if (!open) (void)hipEventRecord((hipEvent_t)c->ev_fork, s);
+            (void)hipStreamWaitEvent(q, (hipEvent_t)c->ev_fork, 0);
+            open |= 1u << L.lane;
+        }
+        switch (L.kernel) {
+        case MT_PK_HBM: mtk_hbm(P.full, q, L.n, c->S, c->ops, nullptr); break;
+        case MT_PK_REST: mtk_hbm(P.full, q, L.n, c->S, c->ops, cur); break;      // documents that outgrew LDS
+        case MT_PK_LDS: mtk_lds(P.full, q, L.n, c->S, c->ops, cur, L.l0, L.l1, L.l2); break;
+        case MT_PK_BLK: mtk_blk_fast(q, L.n, c->S, c->ops, L.runs, cur, L.l1, L.l2, L.pad); break;   // never FULL
+        case MT_PK_BLK_CONT: (P.full ? mtk_blk_full : mtk_blk_fast_cont)(q, L.n, c->S, c->ops, L.runs, cur, L.l1, L.l2, L.pad); break;
+        case MT_PK_BLKW: mtk_blkw(q, L.n, c->S, c->ops, L.runs, cur); break;    // never FULL; its caps are compiled in
+        case MT_PK_BIG: mtk_big(P.full, q, L.n, c->S, c->ops, L.runs, cur, L.l0, L.l1, L.l2); break;
+        }
+    }
+    join();
     (void)hipEventRecord((hipEvent_t)c->ev1, s);
     c->ev_pending = true;
     return mtb_check(c);
 }
-static int mtb_launch_open(mt_ctx* c, uint32_t first, uint32_t n) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(mt_open_kernel, dim3(n), dim3(64), 0, (hipStream_t)c->stream, c->S, first);
-    return mtb_check(c);
-}
-static int mtb_launch_load(mt_ctx* c, const MtLoad& L, uint32_t n) {
+// One launch of `n` workgroups of `threads` threads on the context's stream (none for n == 0).
+template <class K, class... A> static int mtb_launch(mt_ctx* c, K kernel, uint32_t n, uint32_t threads, A... a) {
     if (!n) return MT_OK;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(mt_load_kernel, dim3(n), dim3(64), 0, (hipStream_t)c->stream, c->S, L);
+    hipLaunchKernelGGL(kernel, dim3(n), dim3(threads), 0, (hipStream_t)c->stream, a...);
     return mtb_check(c);
 }
+static int mtb_launch_open(mt_ctx* c, uint32_t first, uint32_t n) { return mtb_launch(c, mt_open_kernel, n, 64, c->S, first); }
+static int mtb_launch_load(mt_ctx* c, const MtLoad& L, uint32_t n) { return mtb_launch(c, mt_load_kernel, n, 64, c->S, L); }
 static int mtb_launch_update_seq(mt_ctx* c, const uint32_t* docs, const int32_t* msn, const int32_t* seq, uint32_t n) {
-    if (!n) return MT_OK;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(mt_update_seq_kernel, dim3(n), dim3(64), 0, (hipStream_t)c->stream, c->S, docs, msn, seq);
-    return mtb_check(c);
+    return mtb_launch(c, mt_update_seq_kernel, n, 64, c->S, docs, msn, seq);
 }
 static int mtb_launch_get_length(mt_ctx* c, const uint32_t* docs, const int32_t* ref, const int32_t* cli, int32_t* out, uint32_t n) {
-    if (!n) return MT_OK;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(mt_get_length_kernel, dim3(n), dim3(64), 0, (hipStream_t)c->stream, c->S, docs, ref, cli, out);
-    return mtb_check(c);
+    return mtb_launch(c, mt_get_length_kernel, n, 64, c->S, docs, ref, cli, out);
 }
-
 static int mtb_launch_query(mt_ctx* c, const MtQuery* q, const uint32_t* grp, MtQueryOut* out, uint32_t n_groups) {
-    if (!n_groups) return MT_OK;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(mt_query_kernel, dim3(n_groups), dim3(64), 0, (hipStream_t)c->stream, c->S, q, grp, out);
-    return mtb_check(c);
+    return mtb_launch(c, mt_query_kernel, n_groups, 64, c->S, q, grp, out);
 }
 static int mtb_launch_gather_text(mt_ctx* c, const unsigned long long* at, const uint32_t* len, const unsigned long long* off,
                                   uint16_t* dst, uint32_t n) {
-    if (!n) return MT_OK;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(mt_gather_text_kernel, dim3(n), dim3(256), 0, (hipStream_t)c->stream, c->S.text, at, len, off, dst);
-    return mtb_check(c);
+    return mtb_launch(c, mt_gather_text_kernel, n, 256, (const uint16_t*)c->S.text, at, len, off, dst);
 }
-
 static int mtb_launch_rows(mt_ctx* c, bool pack, uint32_t first, uint32_t n, uint32_t L, const uint64_t* dst, uint64_t* rows,
                            uint64_t* cs) {
-    if (!n) return MT_OK;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(mt_rows_kernel, dim3(n), dim3(64), 0, (hipStream_t)c->stream, c->ops, pack ? 1 : 0, first, L, dst,
-                       (unsigned long long*)rows, cs);
-    return mtb_check(c);
+    return mtb_launch(c, mt_rows_kernel, n, 64, c->ops, pack ? 1 : 0, first, L, dst, (unsigned long long*)rows, cs);
 }
 static int mtb_launch_pack_size(mt_ctx* c, const uint32_t* docs, MtPackSize* out, uint32_t n, uint32_t epoch) {
-    if (!n) return MT_OK;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(mt_pack_size_kernel, dim3(n), dim3(64), 0, (hipStream_t)c->stream, c->S, docs, out, epoch);
-    return mtb_check(c);
+    return mtb_launch(c, mt_pack_size_kernel, n, 64, c->S, docs, out, epoch);
 }
 static int mtb_launch_pack(mt_ctx* c, const uint32_t* docs, const uint64_t* off, uint8_t* stage, uint32_t n, uint32_t epoch) {
-    if (!n) return MT_OK;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(mt_pack_kernel, dim3(n), dim3(64), 0, (hipStream_t)c->stream, c->S, docs, off, stage, epoch);
-    return mtb_check(c);
+    return mtb_launch(c, mt_pack_kernel, n, 64, c->S, docs, off, stage, epoch);
 }
 #define MTB_HAVE_RELOCATE 1
 static int mtb_launch_occupancy(mt_ctx* c, const uint32_t* docs, MtOcc* out, uint32_t n, uint32_t epoch) {
-    if (!n) return MT_OK;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(mt_occupancy_kernel, dim3(n), dim3(64), 0, (hipStream_t)c->stream, c->S, docs, out, epoch);
-    return mtb_check(c);
+    return mtb_launch(c, mt_occupancy_kernel, n, 64, c->S, docs, out, epoch);
 }
 static int mtb_launch_relocate(mt_ctx* c, const uint32_t* docs, const MtDocLayout* ny, uint32_t n, uint32_t epoch, bool compact) {
-    if (!n) return MT_OK;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(mt_relocate_kernel, dim3(n), dim3(64), 0, (hipStream_t)c->stream, c->S, docs, ny, epoch, compact ? 1 : 0);
-    return mtb_check(c);
+    return mtb_launch(c, mt_relocate_kernel, n, 64, c->S, docs, ny, epoch, compact ? 1 : 0);
 }
 
 #define MT_FN(name) mt_##name

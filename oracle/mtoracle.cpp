@@ -1459,6 +1459,7 @@ static uint32_t apply_run(Doc& d, const mt_op_batch* b, uint32_t run) {
         int ty = b->type[i]; unsigned fl = b->flags[i];
         int cl = d.shortId(b->client[i]);                                                        // applyMsg :825
         int seq = b->seq[i], ref = b->ref_seq[i], msn = b->msn[i];
+        t.curOp = (int)(i - o0);                                                                 // delta capture: the op record's index
         if (ty != MT_OP_NOOP) {
             if (t.currentSeq >= seq) t.status |= MT_DS_ASSERT_SEQ;                              // completeAndLogOp :482
             if (t.minSeq > msn) t.status |= MT_DS_ASSERT_MSN;                                   // :484

@@ -30,39 +30,32 @@ static void* mtb_stage_get(mt_ctx* c, size_t n) {
     return st.p;
 }
 static void mtb_stage_send(mt_ctx* c, void* dev, size_t n) { memcpy(dev, c->stage[c->stage_k].p, n); c->stage_k ^= 1; }
-// FULL as on the device: the capture instantiation only while a delta buffer is armed.
-// The same per-run function as the device kernels (mt_replay_doc), one run at a time.
+static uint32_t mtb_cu_count(mt_ctx*) { return 256; }                // an MI355X's CUs
+#include "../../fluidframework_amd/csrc/mt_plan.h"
+
+// The plan's launches (mt_plan.h), as the device issues them, one after another: each workgroup
+// is one call of the per-run function the device kernels call (mt_replay_doc).
 template <bool FULL>
-static void replay_runs(mt_ctx* c, uint32_t n_runs) {
+static void replay_runs(mt_ctx* c, const MtPlan& P) {
     uint32_t* cursor = (uint32_t*)c->b_cursor.p;
-    for (uint32_t run = 0; run < n_runs; run++) {
-        MtScratch sc;
-        if (c->use_lds == 3) cursor[run] = mt_replay_doc<MT_RES_BIG, FULL>(c->S, c->ops, run, &sc, c->lds_rows, c->lds_blks, c->lds_heap);
-        else if (c->use_lds == 2 && c->big_min_ops && c->run_off.size() == n_runs + 1 &&
-                 c->run_off[run + 1] - c->run_off[run] >= c->big_min_ops)      // size classes (mt_set_size_class)
-            cursor[run] = FULL ? mt_replay_doc<MT_RES_BIG, FULL>(c->S, c->ops, run, &sc, MT_G_WIN, 0, MT_G_HEAP)
-                               : mt_replay_doc<MT_RES_BLKW, FULL, true>(c->S, c->ops, run, &sc, 0, MT_BW_BLKS, MT_BW_HEAP);
-        else if (c->use_lds == 2) {                       // long runs (and FULL) continue in-wave, as on the device
-            bool anyLong = c->run_off.size() != n_runs + 1;
-            for (uint32_t q = 0; q < n_runs && !anyLong; q++) anyLong = c->run_off[q + 1] - c->run_off[q] >= c->cont_min_ops;
-            const bool cont = FULL || c->part_cus || c->big_min_ops || anyLong;
-            cursor[run] = cont ? mt_replay_doc<MT_RES_BLK, FULL, true>(c->S, c->ops, run, &sc, 0, c->lds_blks, c->lds_heap)
-                               : mt_replay_doc<MT_RES_BLK, FULL, false>(c->S, c->ops, run, &sc, 0, c->lds_blks, c->lds_heap);
+    for (int i = 0; i < P.n; i++) {
+        const MtLaunch& L = P.l[i];
+        for (uint32_t w = 0; w < L.n; w++) {
+            const uint32_t run = L.runs ? L.runs[w] : w;
+            MtScratch sc;
+            switch (L.kernel) {
+            case MT_PK_HBM: (void)mt_replay_doc<MT_RES_HBM, FULL>(c->S, c->ops, run, &sc, L.l0, L.l1, L.l2); break;
+            case MT_PK_REST: mt_replay_doc_rest<FULL>(c->S, c->ops, run, &sc, cursor[run]); break;
+            case MT_PK_LDS: cursor[run] = mt_replay_doc<MT_RES_LDS, FULL>(c->S, c->ops, run, &sc, L.l0, L.l1, L.l2); break;
+            case MT_PK_BLK: cursor[run] = mt_replay_doc<MT_RES_BLK, FULL, false>(c->S, c->ops, run, &sc, L.l0, L.l1, L.l2); break;
+            case MT_PK_BLK_CONT: cursor[run] = mt_replay_doc<MT_RES_BLK, FULL, true>(c->S, c->ops, run, &sc, L.l0, L.l1, L.l2); break;
+            case MT_PK_BLKW: cursor[run] = mt_replay_doc<MT_RES_BLKW, FULL, true>(c->S, c->ops, run, &sc, L.l0, L.l1, L.l2); break;
+            case MT_PK_BIG: cursor[run] = mt_replay_doc<MT_RES_BIG, FULL>(c->S, c->ops, run, &sc, L.l0, L.l1, L.l2); break;
+            }
         }
-        else if (c->use_lds) cursor[run] = mt_replay_doc<MT_RES_LDS, FULL>(c->S, c->ops, run, &sc, c->lds_rows, c->lds_blks, c->lds_heap);
-        else (void)mt_replay_doc<MT_RES_HBM, FULL>(c->S, c->ops, run, &sc, 0, 0, 0);
-    }
-    for (uint32_t run = 0; run < n_runs && (c->use_lds == 1 || (c->use_lds == 2 && !FULL)); run++) {
-        MtScratch sc;
-        mt_replay_doc_rest<FULL>(c->S, c->ops, run, &sc, cursor[run]);
     }
 }
-// Same two launches as the device (mt_engine.hip): LDS-resident pass, then the
-// HBM pass resuming at each run's cursor.
-static void mt_auto_partition(mt_ctx* c);
-static uint32_t mtb_cu_count(mt_ctx*) { return 256; }                // an MI355X's CUs
 static int mtb_launch_replay(mt_ctx* c, const MtGen& g, uint32_t n_runs) {
-    if (!g.enabled) mt_auto_partition(c);
     if (g.enabled) {
         for (uint32_t run = 0; run < n_runs; run++) {
             MtScratch sc; int lastRef[64];
@@ -73,8 +66,10 @@ static int mtb_launch_replay(mt_ctx* c, const MtGen& g, uint32_t n_runs) {
         }
         return MT_OK;
     }
-    if (c->ops.drec || c->batch_reg || c->batch_wide) replay_runs<true>(c, n_runs);
-    else replay_runs<false>(c, n_runs);
+    MtPlan P;
+    if (int rc = mt_plan_replay(c, mt_replay_full(c), P)) return rc;
+    if (P.full) replay_runs<true>(c, P);
+    else replay_runs<false>(c, P);
     return MT_OK;
 }
 static int mtb_launch_open(mt_ctx* c, uint32_t first, uint32_t n) {
@@ -151,6 +146,20 @@ extern "C" int emu_test_heap(mt_ctx* c, uint32_t doc, const int32_t* ops, int n,
         if (e.status) return -1;
     }
     return np;
+}
+
+// Test hook: the replay plan of the resident batch for a given FULL (mt_plan.h mt_plan_replay),
+// five ints per launch: kernel, lane, n, pad, whether it has a run list.  Returns the number of
+// launches (at most four), or -1 if the plan could not be made.
+extern "C" int emu_test_plan(mt_ctx* c, int full, int32_t* out) {
+    MtPlan P;
+    if (mt_plan_replay(c, full != 0, P)) return -1;
+    for (int i = 0; i < P.n; i++) {
+        const MtLaunch& L = P.l[i];
+        const int32_t row[5] = {L.kernel, L.lane, (int32_t)L.n, (int32_t)L.pad, L.runs != nullptr};
+        memcpy(out + 5 * i, row, sizeof row);
+    }
+    return P.n;
 }
 
 #if defined(MT_WTRACE)

@@ -2,13 +2,15 @@
 append-only inserts with alternating segment properties (no coalescing), a
 device checkpoint of that state, then a deep-window stream generated on top of
 it (continue_docs) and replayed from the restored checkpoint."""
+import functools
+
 import numpy as np
 import pytest
 
 from emu_lib import emu_engine
 from fluidframework_amd.engine import Engine
 from fluidframework_amd.batch import concat_runs as concat
-from oracle_lib import gen_params, generate, replay
+from oracle_lib import OracleDoc, gen_params, generate, replay
 from test_emu_parity import NAMES, ann_props
 
 
@@ -98,16 +100,40 @@ def test_gpu_config4_downscaled_matches_oracle(lag, res):
                       rows=40000, window=16384, text=1 << 18, psets=40000, residency=res)
 
 
-def check_size_classes(factory, counts, big_min_ops, partition_cus=0):
-    """mt_set_size_class: the longer runs of a batch go to the long-document kernel (LDS heap,
-    window and U set) while the rest stay under block residency; every document must still
-    match the oracle."""
+@functools.lru_cache(maxsize=None)
+def size_class_batch(counts):
+    """One generated batch with counts[d] messages for document d, and its property table."""
     props = ann_props()
     n = len(counts)
     p = gen_params(seed=77, n_docs=n, ops=8, clients=5, lag=48, ins=60, rem=30, ins_len=8, rem_len=8, ann_sets=24,
                    rewrite=5)
     batch, st, _ = generate(p, props, ops_per_doc=counts, clients_per_doc=[5] * n)
     assert st == [0] * n
+    return batch, props
+
+
+@functools.lru_cache(maxsize=None)
+def size_class_oracle(counts):
+    """The oracle's documents after that batch, with their delta callbacks recorded: the one
+    reference of every size-class test (read, never changed)."""
+    batch, props = size_class_batch(counts)
+    docs = []
+    for d in range(len(counts)):
+        od = OracleDoc(True, props, NAMES)
+        od.delta_capture()
+        assert od.apply_run(batch, d) == 0
+        docs.append(od)
+    return docs
+
+
+def check_size_classes(factory, counts, big_min_ops, partition_cus=0, capture=False):
+    """mt_set_size_class: the longer runs of a batch go to the long-document kernel (LDS heap,
+    window and U set) while the rest stay under block residency; every document must still
+    match the oracle.  capture: a delta buffer with room for every record is armed, so the
+    batch replays in the FULL kernels, and the records must equal the oracle's callbacks."""
+    counts = tuple(counts)
+    n = len(counts)
+    batch, props = size_class_batch(counts)
     eng = factory(n, rows_per_doc=3 * max(counts) + 64, window_per_doc=8192, propsets_per_doc=2 * max(counts) + 64,
                   text_per_doc=8 * max(counts) + 4096)
     eng.upload_props(props)
@@ -117,6 +143,8 @@ def check_size_classes(factory, counts, big_min_ops, partition_cus=0):
         eng.set_partition(big_min_ops, partition_cus)   # long runs on reserved CUs, one per SIMD
     else:
         eng.set_size_class(big_min_ops)
+    if capture:
+        eng.delta_capture(1 << 20)
     eng.open_docs(0, n)
     eng.apply(batch)
     eng.sync()
@@ -124,28 +152,76 @@ def check_size_classes(factory, counts, big_min_ops, partition_cus=0):
     last = batch.op_offsets[1:] - 1
     neg = np.full(n, -1, np.int32)
     dig = eng.snapshot_digests(range(n), neg, neg, threads=2)
-    for d, (od, ost) in enumerate(replay(batch, props, NAMES)):
-        assert ost == 0
+    oracle = size_class_oracle(counts)
+    for d, od in enumerate(oracle):
         assert eng.get_text([d])[0] == od.get_text(), d
         assert np.array_equal(eng.dump(d), od.dump()), d
         assert int(dig[d]) == od.snapshot(int(batch.arrays["msn"][last[d]]), int(batch.arrays["seq"][last[d]]))[1], d
+    if capture:
+        check_delta_equal(eng, batch, oracle)
+
+
+def check_delta_equal(eng, batch, oracle):
+    """The engine's delta / maintenance records of `batch` equal the oracle documents' callbacks
+    record for record (as tests/test_message_surface.py check_delta_records compares them)."""
+    from fluidframework_amd.jsjson import stringify
+    js = lambda v: None if v is None else stringify(v)
+    recs = eng.delta_records()
+    offs = batch.op_offsets
+    for d, od in enumerate(oracle):
+        mine = recs[(recs["op"] >= offs[d]) & (recs["op"] < offs[d + 1])]
+        want = od.delta_records()
+        assert len(mine) == len(want), f"doc {d}: {len(mine)} vs {len(want)} records"
+        got4 = np.stack([mine["op"].astype(np.int64) - int(offs[d]), mine["kind"], mine["pos"], mine["len"]], 1)
+        want4 = np.array([w[:4] for w in want], np.int64).reshape(len(want), 4)
+        assert np.array_equal(got4, want4), f"doc {d}: record {np.flatnonzero((got4 != want4).any(1))[:1]}"
+        for i, (x, w) in enumerate(zip(mine, want)):
+            kind, b, pa, pb = w[1], w[4], w[5], w[6]
+            if kind in (-1, -2):
+                assert int(x["b"]) == b, (d, i)
+            if kind == 0:
+                assert js(eng.pset_dict(d, int(x["a"]))) == js(pb), (d, i)
+            if kind == 2:
+                assert (js(eng.pset_dict(d, int(x["a"]))), js(eng.pset_dict(d, int(x["b"])))) == (js(pa), js(pb)), (d, i)
+
+
+GPU_COUNTS = [300, 2500, 80, 1200, 40, 3000, 9000, 700] * 4      # 9,000-op runs outgrow the 104-block kernel's LDS
 
 
 def test_size_classes_match_oracle_on_emulation():
     check_size_classes(emu_engine, [300, 2500, 80, 1200, 40, 3000], 1000)
 
 
+def test_size_classes_capture_matches_oracle_on_emulation():
+    check_size_classes(emu_engine, [300, 2500, 80, 1200, 40, 3000], 1000, capture=True)
+
+
 @pytest.mark.gpu
 def test_size_classes_match_oracle_on_gpu():
-    check_size_classes(lambda n, **kw: Engine(n, device=0, **kw), [300, 2500, 80, 1200, 40, 3000, 9000, 700] * 4, 1000)
+    check_size_classes(lambda n, **kw: Engine(n, device=0, **kw), GPU_COUNTS, 1000)
+
+
+@pytest.mark.gpu
+def test_size_classes_capture_matches_oracle_on_gpu():
+    """FULL under size classes: the long runs in the long-document kernel on the second stream."""
+    check_size_classes(lambda n, **kw: Engine(n, device=0, **kw), GPU_COUNTS, 1000, capture=True)
 
 
 def test_partition_classes_match_oracle_on_emulation():
     check_size_classes(emu_engine, [300, 2500, 80, 1200, 40, 3000], 1000, partition_cus=8)
 
 
+def test_partition_classes_capture_matches_oracle_on_emulation():
+    check_size_classes(emu_engine, [300, 2500, 80, 1200, 40, 3000], 1000, partition_cus=8, capture=True)
+
+
 @pytest.mark.gpu
 def test_partition_classes_match_oracle_on_gpu():
     """mt_set_partition: the long runs on CU-masked stream A with padded LDS, the rest on B."""
-    check_size_classes(lambda n, **kw: Engine(n, device=0, **kw), [300, 2500, 80, 1200, 40, 3000, 9000, 700] * 4, 1000,
-                       partition_cus=32)
+    check_size_classes(lambda n, **kw: Engine(n, device=0, **kw), GPU_COUNTS, 1000, partition_cus=32)
+
+
+@pytest.mark.gpu
+def test_partition_classes_capture_matches_oracle_on_gpu():
+    """FULL under a partition: block residency with the in-wave continuation on both masked streams."""
+    check_size_classes(lambda n, **kw: Engine(n, device=0, **kw), GPU_COUNTS, 1000, partition_cus=32, capture=True)
