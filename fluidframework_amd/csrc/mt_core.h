@@ -153,7 +153,7 @@ enum { MT_BIGF_NO_BCACHE = 1, MT_BIGF_NO_PREFETCH = 2, MT_BIGF_NO_TABLE = 4, MT_
 enum { MT_RES_HBM = 0, MT_RES_LDS = 1, MT_RES_BLK = 2, MT_RES_BIG = 3, MT_RES_BLKW = 4 };
 // Diagnostic builds keep per-document phase/event counters (prof[]) across binds;
 // product builds never load or store them (8 SGPR pairs fewer live in the replay loop).
-#if defined(MT_PROFILE) || defined(MT_PROFILE2) || defined(MT_PROFILE3) || defined(MT_PROFILE4) || defined(MT_BPC_STATS) || defined(MT_EVCOUNT3) || defined(MT_EVCOUNT) || defined(MT_EVCOUNT2)
+#if defined(MT_PROFILE) || defined(MT_PROFILE2) || defined(MT_PROFILE3) || defined(MT_PROFILE4) || defined(MT_BPC_STATS) || defined(MT_EVCOUNT3) || defined(MT_EVCOUNT) || defined(MT_EVCOUNT2) || defined(MT_EVRANGE)
 #define MT_KEEP_PROF 1
 #else
 #define MT_KEEP_PROF 0
@@ -181,6 +181,15 @@ enum { MT_RES_HBM = 0, MT_RES_LDS = 1, MT_RES_BLK = 2, MT_RES_BIG = 3, MT_RES_BL
 #define MT_EV2(i, v) prof[i] += (unsigned long long)(v)
 #else
 #define MT_EV2(i, v)
+#endif
+// Range-op events (host-emulation diagnostic builds only, -DMT_EVRANGE): 0 range ops, 1 applied
+// in the start walk's leaf visit (rangeLeaf), 2 start and end boundary in one leaf block,
+// 3 of those the block had no room for the splits, 4 of those refused for another reason
+// (client id, side-list overlap, delta capture, rows, window), 5 rows split by rangeLeaf.
+#if defined(MT_EVRANGE)
+#define MT_EVR(i, v) prof[i] += (unsigned long long)(v)
+#else
+#define MT_EVR(i, v)
 #endif
 // Fine-grained latency probes (device diagnostic builds only, -DMT_PROFILE2):
 // 0 walk blkLoad cyc, 1 walk childLens cyc, 2 walk levels, 3 computeU cyc,
@@ -485,8 +494,11 @@ struct __attribute__((aligned(16), may_alias)) MtQ16a { uint32_t x, y, z, w; };
 #ifndef MT_LEAF_ONCE
 #define MT_LEAF_ONCE 1                // walk: leaf rows loaded whole once, splits from registers
 #endif
+#ifndef MT_RANGE_LEAF
+#define MT_RANGE_LEAF 1               // opRange: a range inside one leaf block is applied in the start walk's visit
+#endif
 #ifndef MT_GT_CH
-#define MT_GT_CH 4                    // gatherText: 64-unit chunks loaded before any is stored
+#define MT_GT_CH 4                  // gatherText: 64-unit chunks loaded before any is stored
 #endif
 #ifndef MT_SCOUR_QUADS
 #define MT_SCOUR_QUADS 1              // scourLeaves: rows' first two quads in two wide loads
@@ -535,8 +547,8 @@ struct BlkH { int len, parent, n, height, scour; };
 struct ChildL { int len; bool tie; };
 struct WinI { int id; int delta; int parent; bool live; bool recycle; };
 
-enum { MT_WALK_SPLIT = 0, MT_WALK_INSERT = 1 };
-enum { MT_W_OK = 0, MT_W_NOCHANGE = 1, MT_W_FAIL = 2 };
+enum { MT_WALK_SPLIT = 0, MT_WALK_INSERT = 1, MT_WALK_RANGE = 2 };   // RANGE: SPLIT at a range's start (rangeLeaf)
+enum { MT_W_OK = 0, MT_W_NOCHANGE = 1, MT_W_FAIL = 2, MT_W_RANGED = 3 };   // RANGED: the whole range op is applied
 enum { MT_MAP_REMOVE = 0, MT_MAP_ANNOTATE = 1, MT_MAP_COLLECT = 2 };
 // How an annotate's prop set applies (applyPropSet): plain, rewrite, or a combining op
 // (MT_OPF_COMBINE: incr, MT_PM_INCR_SMIN with a string minValue; MT_OPF_COMBINE |
@@ -2221,10 +2233,151 @@ template <int RES, bool FULL = true> struct MtEngT {
         }
     }
 #endif
+    // A remove or annotate whose whole range lies in the leaf block B that its start walk has
+    // just loaded (MT_RANGE_LEAF): the two boundary splits, the marking of the covered rows,
+    // their window entries and the LRU entry are all made here from the rows in registers
+    // (lf, perspective lengths cl / pre / total, start row j at block offset p), and the
+    // document is left exactly as the end walk and rangeMap would leave it: row ids, child
+    // order, window order, counters, landing spot.  Everything is decided before anything is
+    // written; false = nothing was done and the caller goes on with the three-visit code.
+    MT_HD bool rangeLeaf(int B, int L, const BlkH& h, const LaneArr<int>& ch, const LaneArr<MtRow>& lf,
+                         const LaneArr<ChildL>& cl, const LaneArr<int>& pre, int total, int p, int j, int span, int mode,
+                         int c, int sq, int opset, int pm) {
+        const int n = h.n, pe = p + span;
+        if (span <= 0 || pe > total) return false;           // the end walk would reach B iff pe <= total
+        MT_EVR(2, 1);
+        if (c >= 63 || mode > MT_MAP_ANNOTATE || (FULL && drec != nullptr)) { MT_EVR(4, 1); return false; }
+        const auto len = wave_map(n, [&](int i) MT_LAM { return own(cl, i).len; });
+        const auto meta = wave_map(n, [&](int i) MT_LAM { return own(lf, i).meta; });
+        // The end boundary's row by the walk's rule.  The start split leaves every child's offset
+        // as it is and start < end, so no row before j and neither half's own rule differs from
+        // the unsplit row's.  None found: the position is used up at the block's end (no split).
+        const auto ce = wave_map(n, [&](int i) MT_LAM {
+            const int q = pe - own(pre, i), l = own(len, i);
+            return (bool)((int)(q < l) | ((int)(q == 0) & (int)(l == 0) & (int)own(cl, i).tie));
+        });
+        const int je = wave_first(ce);
+        const int pj = p - wave_at(pre, j), pje = je >= 0 ? pe - wave_at(pre, je) : 0;
+        const uint32_t mj = wave_at(meta, j), mje = je >= 0 ? wave_at(meta, je) : 0u;
+        const int s1 = (int)(pj > 0) & (int)!(mj & MT_M_MARKER), s2 = (int)(pje > 0) & (int)!(mje & MT_M_MARKER);
+        const int ns = s1 + s2;                              // je == j with both: row j becomes three
+        if (n + ns >= MT_MAXN) { MT_EVR(3, 1); return false; }
+        // covered rows: rangeMap's condition (a split row is covered in its half inside the range)
+        const auto cov = wave_map(n, [&](int i) MT_LAM {
+            const int q = own(pre, i), l = own(len, i);
+            return (bool)((int)(l > 0) & (int)(pe - q > 0) & (int)(p - q < l));
+        });
+        const bool rem = mode == MT_MAP_REMOVE;
+        const auto add = wave_map(n, [&](int i) MT_LAM {     // remove: covered rows enter the window
+            return (bool)((int)own(cov, i) & (int)!(own(meta, i) & MT_M_INWIN) & (int)rem);
+        });
+        const bool side = wave_ballot(wave_map(n, [&](int i) MT_LAM {
+            return (bool)((int)own(cov, i) & (int)(own(lf, i).ovl >> 63));
+        })) != 0;
+        const int w1 = s1 & (int)((mj & MT_M_INWIN) != 0), w2 = s2 & (int)((mje & MT_M_INWIN) != 0);
+        const int nadd = wave_count(add);
+        if (side || rfN + ((int)S.rowCap - rowTop) < ns || winN + w1 + w2 + nadd > (int)S.winCap) {
+            MT_EVR(4, 1);
+            return false;
+        }
+        MT_EVR(1, 1); MT_EVR(5, ns); MT_EV2(5, ns); MT_EV2(7, 1);
+        int n1 = -1, n2 = -1;                                 // right halves, in the two walks' order
+        if (s1) n1 = allocRow();
+        if (s2) n2 = allocRow();
+        const int nact = wave_count(cov), first = wave_first(cov);
+        // Lane i holds child i.  Its own row changes in its first quad (len, rseq, meta), its tcap
+        // and, when removed, its third quad (ovl, rcl); the right halves cut from it are written
+        // whole.  All 16-byte stores built from the loaded fields: no second copy of the row.
+        const unsigned long long cbit = 1ull << c;
+        const auto nd = wave_map(n, [&](int i) MT_LAM {
+            const MtRow f = own(lf, i);
+            const int isS = (int)(i == j) & s1, isE = (int)(i == je) & s2, isC = (int)own(cov, i);
+            if (isE) {                                         // end's right half: outside the range
+                MtQ16a* d = (MtQ16a*)&row(n2);
+                d[0] = MtQ16a{(uint32_t)(f.len - pje), (uint32_t)f.seq, (uint32_t)f.rseq, f.meta & ~MT_M_HREF};
+                d[1] = MtQ16a{(uint32_t)(f.toff + pje), (uint32_t)f.props, (uint32_t)B, (uint32_t)(f.tcap - pje)};
+                d[2] = MtQ16a{(uint32_t)f.ovl, (uint32_t)(f.ovl >> 32), f.rcl, 0u};
+            }
+            const int lo = isS ? pj : 0, hi = isE ? pje : f.len;
+            if (isS) {                                         // start's right half: toff, tcap (the rest below)
+                ((MtQ16a*)&row(n1))[1] =
+                    MtQ16a{(uint32_t)(f.toff + pj), (uint32_t)f.props, (uint32_t)B, (uint32_t)((isE ? pje : f.tcap) - pj)};
+            }
+            if (isS | isE) row(own(ch, i)).tcap = isS ? pj : pje;
+            const int gone = (int)((f.meta & MT_M_REMOVED) != 0);
+            const int mark = isC & (int)rem, fresh = mark & (gone ^ 1);      // fresh: this op is the first remover
+            // what a covered row (in place, or the start's right half) carries after the op
+            const uint32_t crs = fresh ? (uint32_t)sq : (uint32_t)f.rseq, crc = fresh ? (uint32_t)c : f.rcl;
+            const unsigned long long cov_ovl = (mark & gone) ? f.ovl | cbit : f.ovl;   // overlapping remove: first remover kept
+            const uint32_t cm = mark ? f.meta | MT_M_REMOVED | MT_M_INWIN : f.meta;
+            const int here = isC & (isS ^ 1);                                 // covered in place
+            MtQ16a* own_ = (MtQ16a*)&row(own(ch, i));
+            if (isS | isE | (here & mark))
+                own_[0] = MtQ16a{(uint32_t)(isS ? pj : hi), (uint32_t)f.seq, here ? crs : (uint32_t)f.rseq, here ? cm : f.meta};
+            if (here & mark) own_[2] = MtQ16a{(uint32_t)cov_ovl, (uint32_t)(cov_ovl >> 32), crc, (uint32_t)f.mid};
+            if (isS) {                                         // start's right half: always covered
+                MtQ16a* d = (MtQ16a*)&row(n1);
+                d[0] = MtQ16a{(uint32_t)(hi - pj), (uint32_t)f.seq, crs, cm & ~MT_M_HREF};
+                d[2] = MtQ16a{(uint32_t)cov_ovl, (uint32_t)(cov_ovl >> 32), crc, 0u};
+            }
+            return fresh ? hi - lo : 0;                        // observer length newly removed
+        });
+        const int obsDelta = -wave_sum8(nd);
+        if (mode == MT_MAP_ANNOTATE) {
+            // the covered rows' new maps, per distinct old map in child order (the rows in
+            // registers are done with: applyPropSet needs the lanes for itself)
+            const auto old = wave_map(n, [&](int i) MT_LAM { return own(lf, i).props; });
+            const auto pid = wave_map(n, [&](int i) MT_LAM { return ((int)(i == j) & s1) ? n1 : own(ch, i); });
+            int lastOld = -2, lastNew = -1;
+            for (uint64_t b = wave_ballot(cov); b; b &= b - 1) {
+                const int i = __builtin_ctzll(b), o = wave_at(old, i);
+                if (o != lastOld) { lastNew = applyPropSet(o, opset, pm, sq); lastOld = o; }
+                row(wave_at(pid, i)).props = lastNew;
+            }
+        }
+        // window: the halves of rows in it (as each split adds them), then the covered rows
+        if (w1) winSet(winN++, n1);
+        if (w2) winSet(winN++, n2);
+        if (nadd) {
+            const auto rk = wave_rank(add);
+            const int w0 = winN;
+            wave_for(n, [&](int i) MT_LAM {
+                if (own(add, i)) winSet(w0 + own(rk, i), ((int)(i == j) & s1) ? n1 : own(ch, i));
+            });
+            winN += nadd;
+        }
+        if (winN > winHW) winHW = winN;
+        if (ns) {                                            // the block's children, once
+            wave_for(n, [&](int i) MT_LAM { bk(B).c[i + (s1 & (int)(i > j)) + (s2 & (int)(i > je))] = own(ch, i); });
+            if (s1) bk(B).c[j + 1] = n1;
+            if (s2) bk(B).c[je + 1 + s1] = n2;
+            bk(B).n = n + ns;
+            landB = B;
+        }
+        if (rem) {
+            bk(B).len = h.len + obsDelta;
+            if (L > 0 && obsDelta != 0) {                    // ancestors on the path: one lane per level
+                wave_for(L, [&](int l) MT_LAM { const int pb = sc->pathB[l]; bk(pb).len = bk(pb).len + obsDelta; });
+                wave_sync();
+            }
+        }
+        if (first >= 0) {
+            const bool half = first == j && s1;
+            const uint32_t m0 = half ? mj & ~MT_M_HREF : wave_at(meta, first);
+            addToLRUSetKnown(half ? n1 : wave_at(ch, first), sq, B, rem ? m0 | MT_M_REMOVED | MT_M_INWIN : m0);
+        }
+        c_rows += 2u * (uint32_t)(ns + nact);
+        lastL = L; lastSplit = false; uValid = false;
+        lastIdx = je < 0 ? n + s1 : (s2 ? je + 1 + s1 : je + (s1 & (int)(je > j)));
+        return true;
+    }
     // insertingWalk (MT/mergeTree.ts:2363-2493) for one remote op perspective.  L0 > 0
     // resumes at level L0 of the previous walk's path (pathB/pathJ/pathOff above L0 still
     // valid, U unchanged): the root descent would pick the same children down to there.
-    MT_HD int walk(int kind, int pos, int r, int c, int cand, int candLen, int L0 = 0) {
+    // MT_WALK_RANGE: a split walk to the start of the range op [pos, rEnd) (mode, sequence
+    // number, property set and mode as opRange's): MT_W_RANGED if rangeLeaf applied the whole op.
+    MT_HD int walk(int kind, int pos, int r, int c, int cand, int candLen, int L0 = 0, int rEnd = 0, int rMode = 0,
+                   int rSq = 0, int rOpset = -1, int rPm = 0) {
         if (!(uValid && uRef == r && uCli == c)) { computeU(r, c, false); L0 = 0; }
         int B = root, L = 0, p = pos;
         if (L0 > 0) { B = uni(sc->pathB[L0]); L = L0; p = pos - uni(sc->pathOff[L0]); }
@@ -2279,7 +2432,11 @@ template <int RES, bool FULL = true> struct MtEngT {
                 }
                 const int s = wave_at(ch, j);
                 lastL = L; lastSplit = false;
-                if (kind == MT_WALK_SPLIT) {
+                if (MT_RANGE_LEAF && MT_LEAF_ONCE && kind == MT_WALK_RANGE) {
+                    if (rangeLeaf(B, L, h, ch, lf, cl, pre, total, p, j, rEnd - pos, rMode, c, rSq, rOpset, rPm))
+                        return MT_W_RANGED;
+                }
+                if (kind != MT_WALK_INSERT) {
                     const uint32_t sm = MT_LEAF_ONCE ? (uint32_t)wave_at(leafField(lf, j, 3), j) : uni(row(s).meta);
                     if (pj > 0 && !(sm & MT_M_MARKER)) {
                         const int n = MT_LEAF_ONCE ? splitRowKnown(s, pj, lf, j) : splitRow(s, pj);
@@ -2307,7 +2464,7 @@ template <int RES, bool FULL = true> struct MtEngT {
             }
             if (p - total == 0) {
                 lastL = L; lastIdx = h.n; lastSplit = false;
-                if (kind == MT_WALK_SPLIT) return MT_W_NOCHANGE;
+                if (kind != MT_WALK_INSERT) return MT_W_NOCHANGE;
                 insertAtPath(L, h.n, cand, candLen);          // position used up at a block end: append
                 uValid = false;
                 return MT_W_OK;
@@ -2383,7 +2540,7 @@ template <int RES, bool FULL = true> struct MtEngT {
                 const int dk = 31 - __builtin_clz((unsigned)k);
                 wave_for(n + 1, [&](int i) MT_LAM {
                     if (i < 1 || i > k) return;
-                    const int di = 31 - __builtin_clz((unsigned)i);
+                    const int di = 31 - __builtin_clz((unsigned)mt_opaque(i));   // not hoisted to the kernel's entry
                     if ((k >> (dk - di)) != i) return;
                     if (i == k) { hp(i).seg = lseg; hp(i).maxSeq = lms; }
                     else { hp(i).seg = own(cs, i); hp(i).maxSeq = own(cm, i); }
@@ -3238,7 +3395,13 @@ template <int RES, bool FULL = true> struct MtEngT {
                             if (rec) emitDelta(MT_DK_ANNOTATE, base + wave_at(opre, j), uni(row(s).len), s, old, nw);
                         }
                     }
-                    if (mode != MT_MAP_COLLECT) addToLRUSet(wave_at(ch, first), sq);
+                    // the first row's parent is B and its meta is what the stores above left
+                    if (mode != MT_MAP_COLLECT) {
+                        if (MT_RANGE_LEAF && !status) {
+                            const uint32_t m0 = wave_at(lm, first);
+                            addToLRUSetKnown(wave_at(ch, first), sq, B, mode == MT_MAP_REMOVE ? m0 | MT_M_REMOVED | MT_M_INWIN : m0);
+                        } else addToLRUSet(wave_at(ch, first), sq);
+                    }
                 }
                 if (mode == MT_MAP_REMOVE) bk(B).len = h.len + obsDelta;
                 const int d = wave_at(fD, L) + obsDelta;
@@ -3628,7 +3791,14 @@ template <int RES, bool FULL = true> struct MtEngT {
     }
     MT_HD void opRange(int mode, int start, int end, int r, int c, int sq, int opset, int pm) {
         MT_PB(t0);
-        int w = walk(MT_WALK_SPLIT, start, r, c, -1, 0);
+        MT_EVR(0, 1);
+        int w = walk(MT_RANGE_LEAF ? MT_WALK_RANGE : MT_WALK_SPLIT, start, r, c, -1, 0, 0, end, mode, sq, opset, pm);
+        if (MT_RANGE_LEAF && w == MT_W_RANGED) {              // applied whole in the start walk's leaf visit
+            MT_PE(MT_PH_SPLIT, t0);
+            if (status) return;
+            zamboni();
+            return;
+        }
         if (w == MT_W_OK) c_rows += 2;
         if (status) return;
         // The end boundary's walk resumes at the deepest block of the start walk's path whose
