@@ -1121,7 +1121,7 @@ int MT_FN(set_residency)(mt_ctx* c, int use_lds, int rows, int blocks, int heap)
         return MT_E_INVALID;
     c->use_lds = use_lds;
     c->lds_rows = rows ? rows : (use_lds == 3 ? MT_G_WIN : MT_L_ROWS);   // 3: window entries in LDS
-    // 3: blocks = MT_BIGF_* switches (block cache, zamboni prefetch, corrections table, parent cache off; A/B)
+    // 3: blocks = MT_BIGF_* switches (bit 0 reserved, no effect; zamboni prefetch, corrections table, parent cache off; A/B)
     c->lds_blks = use_lds == 3 ? blocks : (blocks ? blocks : (use_lds == 2 ? MT_B_BLKS : MT_L_BLKS));
     c->lds_heap = heap ? heap : maxHeap;
     return MT_OK;

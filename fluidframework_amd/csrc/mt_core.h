@@ -33,10 +33,7 @@
 #define MT_PSK 16                     // property keys per MtPSet chunk
 #define MT_PKEYS MT_MAX_PROP_KEYS      // keys of one property map (more: PROPS_TOO_MANY); up to a
                                       // wave's 64 one per lane, past that in the pool (applyPropSetWide)
-#ifndef MT_PATH_RESUME
-#define MT_PATH_RESUME 1              // opRange: end walk and range walk start below the root
-#endif
-#define MT_MAXN 8                     // MaxNodesInBlock, MT/mergeTree.ts:350
+#define MT_MAXN 8                    // MaxNodesInBlock, MT/mergeTree.ts:350
 #define MT_GRAN 256                   // TextSegmentGranularity, MT/mergeTree.ts:1056
 #define MT_ZMAX 2                     // zamboniSegmentsMaxCount, MT/mergeTree.ts:1058
 #define MT_NOREM 0x7FFFFFFF           // removedSeq "undefined"
@@ -96,23 +93,7 @@
 #define MT_G_WIN 2048
 #endif
 #define MT_G_H 12                     // ancestor-chain levels kept per U entry (tree height < MT_G_H - 2)
-// Long-document residency also keeps an LDS block cache: MT_G_BC direct-mapped slots (slot =
-// block id mod MT_G_BC), write-back, filled by the descents with blocks of height >= MT_G_BCH.
-// A slot holding a higher block is not taken by a lower one, so the top of the tree stays
-// resident and the descents, ancestor chains and path updates reach HBM only near the leaves.
-// Compiled in with -DMT_G_BCACHE=1 only: measured -1 % on config 4 (upper levels already hit
-// L2, and every block access then pays a tag check and flat addressing).
-#ifndef MT_G_BCACHE
-#define MT_G_BCACHE 0
-#endif
-#ifndef MT_G_BC
-#define MT_G_BC (MT_G_BCACHE ? 512 : 1)
-#endif
-#ifndef MT_G_BCH
-#define MT_G_BCH 1
-#endif
-#define MT_BC_EMPTY ((int)0x80000000)
-// ... and runs as a workgroup of MT_G_NW waves: wave 0 applies the ops; the others take
+// It runs as a workgroup of MT_G_NW waves: wave 0 applies the ops; the others take
 // shares of computeU's window scan (MT_G_STG window entries staged in LDS per round) and of
 // its ancestor-chain walks (mwRun / mwShare; the host emulation runs every share in turn).
 #ifndef MT_G_NW
@@ -122,13 +103,12 @@
 #ifndef MT_G_MWMIN
 #define MT_G_MWMIN 512                 // windows up to this many entries are scanned by wave 0 alone
 #endif
-#ifndef MT_G_ALLCH
-#define MT_G_ALLCH 0                   // 1: ... with every chunk's rows loaded in one round trip
-#endif
 enum { MT_MW_EXIT = 0, MT_MW_SCAN = 1, MT_MW_CHAIN = 2, MT_MW_PREFETCH = 3 };
 // Jobs alternate between two LDS slots, so wave 0 can post an asynchronous job (PREFETCH: no
 // completion barrier) and write the next one while helpers still read the last.
-// Runtime switches of the long-document residency (mt_set_residency(ctx, 3, rows, flags, heap)):
+// Runtime switches of the long-document residency (mt_set_residency(ctx, 3, rows, flags, heap)).
+// MT_BIGF_NO_BCACHE is reserved and has no effect: callers still pass the bit, and the block
+// cache it once switched off is gone.
 enum { MT_BIGF_NO_BCACHE = 1, MT_BIGF_NO_PREFETCH = 2, MT_BIGF_NO_TABLE = 4, MT_BIGF_NO_BPC = 8 };
 // Per-block perspective corrections of the long-document residency: an LDS hash table
 // block id -> Σ delta of the U rows under the block, built bottom-up once per U set (each
@@ -138,14 +118,12 @@ enum { MT_BIGF_NO_BCACHE = 1, MT_BIGF_NO_PREFETCH = 2, MT_BIGF_NO_TABLE = 4, MT_
 #ifndef MT_G_HT
 #define MT_G_HT 4096
 #endif
+#define MT_HT_EMPTY ((int)0x80000000)  // a free slot's key
 // Parent cache of the long-document residency: block id -> parent in LDS, direct-mapped, one
 // dword per entry (tag = id >> MT_G_BPL in bits 20..31, parent + 1 in bits 0..19), so htBuild's
 // bottom-up passes read the parents of the blocks it saw for the last U sets from LDS instead
 // of HBM.  Every write of a block's parent field updates it (bpPut / bpDrop); documents with
 // 2^20 blocks or more run without it.
-#ifndef MT_G_BPC
-#define MT_G_BPC 1
-#endif
 #define MT_G_BPL 11
 #define MT_G_BP (1 << MT_G_BPL)
 #define MT_BP_EMPTY 0xFFFFFFFFu
@@ -246,9 +224,6 @@ enum { MT_PH_U = 0, MT_PH_SPLIT, MT_PH_INSERT, MT_PH_RANGE, MT_PH_ZAMBONI, MT_PH
 #define MT_M_HREF1 0x01000000u        // heap-entry reference count, bits 24..31 (saturating)
 #define MT_M_HREF 0xFF000000u
 
-#ifndef MT_ROW64
-#define MT_ROW64 0
-#endif
 struct __attribute__((aligned(16))) MtRow {   // one 48-byte record per segment row
     int len;         // cachedLength (UTF-16 units; 1 for a marker)
     int seq;         // insertion seq
@@ -261,9 +236,6 @@ struct __attribute__((aligned(16))) MtRow {   // one 48-byte record per segment 
     unsigned long long ovl;  // removedClientOverlap: bit c for clients c < 63; bit 63 = more in the side list
     uint32_t rcl;            // removedClientId (16 bits)
     int mid;                 // marker: its markerId's per-document index + 1 (0: none)
-#if MT_ROW64
-    int pad[4];              // one row per 64-byte line (a row's update dirties one line)
-#endif
 };
 struct __attribute__((aligned(16))) MtBlk {   // one 64-byte record per B-tree block
     int c[8];        // children: segment rows (height 0) or blocks
@@ -460,13 +432,15 @@ struct __attribute__((aligned(16))) MtLdsBig {
     int uid[MT_G_U], udelta[MT_G_U];
     int uanc[MT_G_U * MT_G_H];        // block ids (-1 = none)
     uint16_t ulist[MT_G_U];           // a descent's U entries under the current block (walk)
-    MtBlk bc[MT_G_BC];                // block cache (write-back; HBM copies of cached blocks are stale)
-    int btag[MT_G_BC];                // block id held by each slot, MT_BC_EMPTY if none
+    // Unused (68 bytes).  Taking them out moves every member below, and mt_replay_big_kernel
+    // then allocates registers differently, so they stay until that kernel is
+    // next measured.
+    MtBlk spare0; int spare1;
     // computeU's staged window entries (one round): row, delta, (parent + 1) | live << 30 | recycle << 31
     int sid[MT_G_STG], sdel[MT_G_STG], spf[MT_G_STG];
-    int htk[MT_G_HT], htv[MT_G_HT];   // corrections table: block id (MT_BC_EMPTY: free), Σ delta
+    int htk[MT_G_HT], htv[MT_G_HT];   // corrections table: block id (MT_HT_EMPTY: free), Σ delta
     uint16_t hlist[MT_G_HT];          // occupied slots in insertion (level) order
-    uint32_t bpc[MT_G_BP];            // parent cache (MT_G_BPC)
+    uint32_t bpc[MT_G_BP];            // parent cache
     struct Job {                      // a job wave 0 posts to the workgroup (mwRun / mwPost)
         int op, r, c, r0, n, H, minSeq, heapN;
         MtRow* R; int* win; MtBlk* blk; int* uanc; uint16_t* text;
@@ -488,20 +462,11 @@ struct MtScratch {
 // A row record read as 16-byte quads (one wide load per quad); may_alias keeps those accesses
 // ordered with the field accesses of the same record.
 struct __attribute__((aligned(16), may_alias)) MtQ16a { uint32_t x, y, z, w; };
-#ifndef MT_NONL
-#define MT_NONL 1                     // rows flag text without a newline (MT_M_NONL)
-#endif
-#ifndef MT_LEAF_ONCE
-#define MT_LEAF_ONCE 1                // walk: leaf rows loaded whole once, splits from registers
-#endif
 #ifndef MT_RANGE_LEAF
 #define MT_RANGE_LEAF 1               // opRange: a range inside one leaf block is applied in the start walk's visit
 #endif
 #ifndef MT_GT_CH
 #define MT_GT_CH 4                  // gatherText: 64-unit chunks loaded before any is stored
-#endif
-#ifndef MT_SCOUR_QUADS
-#define MT_SCOUR_QUADS 1              // scourLeaves: rows' first two quads in two wide loads
 #endif
 MT_INLINE int pick16(const int* c, int j) {         // c[j] for a lane index j (no private-array indexing)
     int v = c[0];
@@ -572,28 +537,17 @@ struct MtEngParams {
 // the LDS-resident engine (MtEngT<MT_RES_LDS / MT_RES_BLK>) is a ds_* instruction; the host
 // emulation has one static instance (it runs one wave at a time).
 #if defined(__HIP_DEVICE_COMPILE__)
-__shared__ MtLdsPools mt_lds_pools_v;
+#define MT_LDS_VAR(T, v) __shared__ T v
 #else
-static MtLdsPools mt_lds_pools_v;
+#define MT_LDS_VAR(T, v) static T v
 #endif
+MT_LDS_VAR(MtLdsPools, mt_lds_pools_v);
 MT_INLINE MtLdsPools& mt_lds() { return mt_lds_pools_v; }
-#if defined(__HIP_DEVICE_COMPILE__)
-__shared__ MtLdsBlk mt_ldsb_v;
-#else
-static MtLdsBlk mt_ldsb_v;
-#endif
+MT_LDS_VAR(MtLdsBlk, mt_ldsb_v);
 MT_INLINE MtLdsBlk& mt_ldsb() { return mt_ldsb_v; }
-#if defined(__HIP_DEVICE_COMPILE__)
-__shared__ MtLdsBlkW mt_ldsbw_v;
-#else
-static MtLdsBlkW mt_ldsbw_v;
-#endif
+MT_LDS_VAR(MtLdsBlkW, mt_ldsbw_v);
 MT_INLINE MtLdsBlkW& mt_ldsbw() { return mt_ldsbw_v; }
-#if defined(__HIP_DEVICE_COMPILE__)
-__shared__ MtLdsBig mt_ldsg_v;
-#else
-static MtLdsBig mt_ldsg_v;
-#endif
+MT_LDS_VAR(MtLdsBig, mt_ldsg_v);
 MT_INLINE MtLdsBig& mt_ldsg() { return mt_ldsg_v; }
 
 // Cold per-document state of a bound engine: capacities, prop-table pointers, counters,
@@ -619,15 +573,7 @@ struct MtCold {
     int pcKey[4], pcVal[4];                   // newMap: property maps made from an op's set alone
     int pNever;                               // MtDocHdr::pNever
 };
-#if defined(__HIP_DEVICE_COMPILE__)
-__shared__ MtCold mt_cold_v;
-#else
-static MtCold mt_cold_v;
-#endif
-#if defined(MT_DBG_FAIL) && defined(__HIP_DEVICE_COMPILE__)
-struct MtDbg { int s, n; uint32_t op; };     // diagnostic builds: the last row split
-__shared__ MtDbg mt_dbg_v;
-#endif
+MT_LDS_VAR(MtCold, mt_cold_v);
 
 // RES: MT_RES_HBM (every pool in HBM), MT_RES_LDS (rows, blocks, heap, window,
 // U set in LDS) or MT_RES_BLK (blocks and heap in LDS).  FULL: the instantiation can
@@ -668,31 +614,7 @@ template <int RES, bool FULL = true> struct MtEngT {
     MT_HD MtRow& row(int s) const { if constexpr (LDS) return mt_lds().rows[s]; else return R[s]; }
     MT_HD MtBlk& bk(int b) const {
         if constexpr (LDS) return mt_lds().blk[b]; else if constexpr (BLKL) return LB().blk[b];
-        else if constexpr (BIG && MT_G_BCACHE) {        // block cache hit: the LDS copy is the current one
-            const int s = b & (MT_G_BC - 1);
-            return mt_ldsg().btag[s] == b ? mt_ldsg().bc[s] : blk[b];
-        } else return blk[b];
-    }
-    // MT_RES_BIG: install block B (its current record in lanes 0..15) in its cache slot, whose
-    // tag is tg, unless the slot holds a higher live block; the evicted block is written back.
-    MT_HD void bcInstall(int B, int tg, const LaneArr<int>& w, int hb) {
-        if constexpr (BIG && MT_G_BCACHE) {
-            if (!bcOn || hb < MT_G_BCH || tg == B) return;
-            const int s = B & (MT_G_BC - 1);
-            MtLdsBig& G = mt_ldsg();
-            if (tg != MT_BC_EMPTY) {
-                if (uni(G.bc[s].n) >= 0 && uni(G.bc[s].height) > hb) return;
-                const auto old = wave_map(16, [&](int i) MT_LAM { return ((const int*)&G.bc[s])[i]; });
-                wave_for(16, [&](int i) MT_LAM { ((int*)&blk[tg])[i] = own(old, i); });
-            }
-            wave_for(16, [&](int i) MT_LAM { ((int*)&G.bc[s])[i] = own(w, i); });
-            wave_for(1, [&](int) MT_LAM { G.btag[s] = B; });
-            wave_sync();
-        } else { (void)B; (void)tg; (void)w; (void)hb; }
-    }
-    MT_HD int bcTag(int B) const {
-        if constexpr (BIG && MT_G_BCACHE) return uni(mt_ldsg().btag[B & (MT_G_BC - 1)]);
-        else { (void)B; return 0; }
+        else return blk[b];
     }
     MT_HD MtHeapE& hp(int k) const {
         if constexpr (LDS) return mt_lds().heap[k]; else if constexpr (BLKL) return LB().heap[k];
@@ -775,10 +697,9 @@ template <int RES, bool FULL = true> struct MtEngT {
     int heapTop;                        // hp(1).maxSeq cached (INT_MAX when empty)
     int& gcEpoch = mt_cold_v.epoch;     // bumped by every text compaction
     int lastL, lastIdx; bool lastSplit; // landing spot of the last walk; did it split a block
-    bool bcOn;                          // MT_RES_BIG: descents fill the LDS block cache
     bool htOk; int hlistN;              // MT_RES_BIG: the corrections table is built for U; occupied slots
     bool htOn, pfOn; int mwSeq;         // MT_RES_BIG: table / zamboni prefetch enabled; jobs posted so far
-    bool bpOn;                          // MT_RES_BIG: the LDS parent cache is kept (MT_G_BPC)
+    bool bpOn;                          // MT_RES_BIG: the LDS parent cache is kept
     int& nCol = mt_cold_v.ncol;         // rows gathered by rangeMap(MT_MAP_COLLECT) at the register arena's tail
     int landB;                          // leaf block the last insertAtPath linked its node under
     int rfN; int*& rfHbm = mt_cold_v.rfhbm;   // recycled-row stack: depth, HBM home between runs
@@ -823,7 +744,7 @@ template <int RES, bool FULL = true> struct MtEngT {
         c_ops = c_msgs = c_ins = c_rows = c_depth = c_scour = 0;
         nU = 0; uValid = false; uRef = -1; uCli = -1;
         heapTop = heapN > 0 ? uni(heap[1].maxSeq) : 0x7FFFFFFF;     // HBM home: bind precedes toLds
-        lastL = 0; lastIdx = 0; lastSplit = false; gcEpoch = 0; bcOn = false; htOk = false; hlistN = 0; htOn = pfOn = false; mwSeq = 0; bpOn = false;
+        lastL = 0; lastIdx = 0; lastSplit = false; gcEpoch = 0; htOk = false; hlistN = 0; htOn = pfOn = false; mwSeq = 0; bpOn = false;
         for (int i = 0; i < 4; i++) mt_cold_v.pcKey[i] = -1;
         rfHbm = st.hold + (size_t)d * MT_RFL; rfN = uni(h.rfN); blkFreeN = uni(h.blkFreeN);
         heapHW = uni(h.heapHW); winHW = uni(h.winHW); ovxN = uni(h.ovxN);
@@ -896,12 +817,12 @@ template <int RES, bool FULL = true> struct MtEngT {
         return blkTop++;
     }
     MT_HD void freeBlock(int id) { bk(id).parent = blkFree; bk(id).n = -1; blkFree = id; blkFreeN++; bpDrop(id); }
-    // The parent cache (MT_RES_BIG, MT_G_BPC): bpPut after every write of a block's parent field,
+    // The parent cache (MT_RES_BIG): bpPut after every write of a block's parent field,
     // bpDrop when the field stops being a parent (free list), bpReset when block ids are reassigned.
     MT_HD static uint32_t bpPack(int b, int p) { return ((uint32_t)(b >> MT_G_BPL) << 20) | (uint32_t)(p + 1); }
     MT_HD void bpPut(int b, int p) {
         if constexpr (BIG) {
-            if (MT_G_BPC && bpOn) {
+            if (bpOn) {
                 uint32_t& e = mt_ldsg().bpc[b & (MT_G_BP - 1)];
                 if (e != MT_BP_EMPTY && (e >> 20) != (uint32_t)(b >> MT_G_BPL)) MT_BS(4);
                 e = bpPack(b, p);
@@ -910,7 +831,7 @@ template <int RES, bool FULL = true> struct MtEngT {
     }
     MT_HD void bpDrop(int b) {
         if constexpr (BIG) {
-            if (MT_G_BPC && bpOn) {
+            if (bpOn) {
                 uint32_t& e = mt_ldsg().bpc[b & (MT_G_BP - 1)];
                 if ((e >> 20) == (uint32_t)(b >> MT_G_BPL)) MT_BS(5);
                 e = MT_BP_EMPTY;
@@ -919,7 +840,7 @@ template <int RES, bool FULL = true> struct MtEngT {
     }
     MT_HD void bpReset() {
         if constexpr (BIG) {
-            if (MT_G_BPC && bpOn) {
+            if (bpOn) {
                 for (int base = 0; base < MT_G_BP; base += MT_WAVE)
                     wave_for(MT_WAVE, [&](int k) MT_LAM { mt_ldsg().bpc[base + k] = MT_BP_EMPTY; });
                 wave_sync();
@@ -929,7 +850,7 @@ template <int RES, bool FULL = true> struct MtEngT {
     // bk(b).parent, through the parent cache when it is kept (a miss fills the entry).
     MT_HD int bkParent(int b) {
         if constexpr (BIG) {
-            if (MT_G_BPC && bpOn) {
+            if (bpOn) {
                 uint32_t& e = mt_ldsg().bpc[b & (MT_G_BP - 1)];
                 const uint32_t v = e;
                 MT_BS(0);
@@ -975,15 +896,12 @@ template <int RES, bool FULL = true> struct MtEngT {
             MtLdsBig& G = mt_ldsg();
             copyI((int*)G.heap, (const int*)heap, 2 * (heapN + 1));
             copyI(G.win, win, winN < lr ? winN : lr);
-            for (int base = 0; MT_G_BCACHE && base < MT_G_BC; base += MT_WAVE)
-                wave_for(MT_WAVE, [&](int k) MT_LAM { G.btag[base + k] = MT_BC_EMPTY; });
             for (int base = 0; base < MT_G_HT; base += MT_WAVE)
-                wave_for(MT_WAVE, [&](int k) MT_LAM { G.htk[base + k] = MT_BC_EMPTY; G.htv[base + k] = 0; });
+                wave_for(MT_WAVE, [&](int k) MT_LAM { G.htk[base + k] = MT_HT_EMPTY; G.htv[base + k] = 0; });
             htOk = false; hlistN = 0;
-            bcOn = MT_G_BCACHE && !(lb & MT_BIGF_NO_BCACHE);    // lb: MT_BIGF_* switches (A/B)
-            pfOn = MT_G_NW > 1 && !(lb & MT_BIGF_NO_PREFETCH);
+            pfOn = MT_G_NW > 1 && !(lb & MT_BIGF_NO_PREFETCH);  // lb: MT_BIGF_* switches (A/B)
             htOn = !(lb & MT_BIGF_NO_TABLE);
-            bpOn = MT_G_BPC && !(lb & MT_BIGF_NO_BPC) && blkCap < (1u << 20);
+            bpOn = !(lb & MT_BIGF_NO_BPC) && blkCap < (1u << 20);
             bpReset();
             wave_sync();
             gRowCap = S.rowCap; gBlkCap = blkCap; gHeapCap = S.heapCap; gWinCap = S.winCap;
@@ -1030,20 +948,7 @@ template <int RES, bool FULL = true> struct MtEngT {
             MtLdsBig& G = mt_ldsg();
             copyI((int*)heap, (const int*)G.heap, 2 * (heapN + 1));
             copyI(win, G.win, winN < lRows ? winN : lRows);
-            // write the cached blocks back (lane k: slot base + k, four 16-byte quads)
-            for (int base = 0; MT_G_BCACHE && base < MT_G_BC; base += MT_WAVE) {
-                wave_for(MT_WAVE, [&](int k) MT_LAM {
-                    const int t = G.btag[base + k];
-                    if (t != MT_BC_EMPTY) {
-                        const MtQ16* src = (const MtQ16*)&G.bc[base + k];
-                        MtQ16* dst = (MtQ16*)&blk[t];
-                        const MtQ16 a = src[0], b = src[1], c2 = src[2], d = src[3];
-                        dst[0] = a; dst[1] = b; dst[2] = c2; dst[3] = d;
-                    }
-                    G.btag[base + k] = MT_BC_EMPTY;
-                });
-            }
-            bcOn = false; htOk = false; pfOn = false;
+            htOk = false; pfOn = false;
             wave_sync();
             S.heapCap = gHeapCap;
             nU = 0; uValid = false;
@@ -1218,15 +1123,8 @@ template <int RES, bool FULL = true> struct MtEngT {
     // Whole 64-byte block record in one transaction: lane i loads dword i;
     // children stay in lanes 0..n-1, scalar fields are broadcast to SGPRs.
     MT_HD LaneArr<int> blkLoad(int B, BlkH& h) {
-        LaneArr<int> w;
-        int tg = 0;
-        if constexpr (BIG && MT_G_BCACHE) {               // explicit LDS / HBM load, then fill
-            tg = bcTag(B);
-            if (tg == B) w = wave_map(16, [&](int i) MT_LAM { return ((const int*)&mt_ldsg().bc[B & (MT_G_BC - 1)])[i]; });
-            else w = wave_map(16, [&](int i) MT_LAM { return ((const int*)&blk[B])[i]; });
-        } else w = wave_map(16, [&](int i) MT_LAM { return ((const int*)&bk(B))[i]; });
+        const LaneArr<int> w = wave_map(16, [&](int i) MT_LAM { return ((const int*)&bk(B))[i]; });
         h.len = wave_at(w, 8); h.parent = wave_at(w, 9); h.n = wave_at(w, 10); h.height = wave_at(w, 11); h.scour = wave_at(w, 12);
-        if constexpr (BIG && MT_G_BCACHE) bcInstall(B, tg, w, h.height);
         const int n = h.n;
         return wave_map(8, [&](int j) MT_LAM { return j < n ? own(w, j) : -1; });
     }
@@ -1246,12 +1144,10 @@ template <int RES, bool FULL = true> struct MtEngT {
         return wave_map(8, [&](int j) MT_LAM { return j < 4 ? own(a, j) : own(b, j); });
     }
     // child j's record as blkLoad returns it (j uniform)
-    // (MT_RES_BIG: the child, block id b, is installed in the block cache.)
-    MT_HD LaneArr<int> kidRec(const LaneArr<int>& r0, const LaneArr<int>& r1, int j, BlkH& h, int b) {
+    MT_HD static LaneArr<int> kidRec(const LaneArr<int>& r0, const LaneArr<int>& r1, int j, BlkH& h) {
         const int o = (j & 3) << 4;
         const auto w = wave_shfl(j < 4 ? r0 : r1, [o](int t) MT_LAM { return o + (t & 15); });
         h.len = wave_at(w, 8); h.parent = wave_at(w, 9); h.n = wave_at(w, 10); h.height = wave_at(w, 11); h.scour = wave_at(w, 12);
-        if constexpr (BIG && MT_G_BCACHE) { if (bcOn && h.height >= MT_G_BCH) bcInstall(b, bcTag(b), w, h.height); } else (void)b;
         const int n = h.n;
         return wave_map(8, [&](int i) MT_LAM { return i < n ? own(w, i) : -1; });
     }
@@ -1272,7 +1168,6 @@ template <int RES, bool FULL = true> struct MtEngT {
     // and its U delta (perspective length - observer length).
     MT_HD WinI winEntry(int s, int r, int c) const {
         WinI w; w.id = s;
-#if MT_SCOUR_QUADS
         // the row as three 16-byte loads (len seq rseq meta | toff props parent tcap | ovl rcl mid)
         const MtQ16a q0 = ((const MtQ16a*)&row(s))[0], q1 = ((const MtQ16a*)&row(s))[1], q2 = ((const MtQ16a*)&row(s))[2];
         const uint32_t mt = q0.w;
@@ -1280,13 +1175,6 @@ template <int RES, bool FULL = true> struct MtEngT {
         w.parent = (int)q1.z;
         const unsigned long long ovl = (unsigned long long)q2.x | ((unsigned long long)q2.y << 32);
         const uint32_t rcl = q2.z;
-#else
-        const uint32_t mt = row(s).meta;
-        const int sq = row(s).seq, rs = row(s).rseq, ln = row(s).len;
-        w.parent = row(s).parent;
-        const unsigned long long ovl = row(s).ovl;
-        const uint32_t rcl = row(s).rcl;
-#endif
         const bool removed = (mt & MT_M_REMOVED) != 0;
         const bool linked = w.parent >= 0;
         w.live = linked && (sq > minSeq || (removed && rs > minSeq));
@@ -1330,7 +1218,7 @@ template <int RES, bool FULL = true> struct MtEngT {
         nU += cntU;
     }
     // Ancestor chains (levels 1..H) of U entries [g0, g0 + 512) from their level-0 entries,
-    // blocks in HBM (or the MT_RES_BIG block cache): the parent loads of one level are
+    // blocks in HBM: the parent loads of one level are
     // independent, so a level costs one round trip for 512 entries.
     MT_HD void chainGroup(int g0, int nu, int H) {
         wave_for(MT_WAVE, [&](int k) MT_LAM {
@@ -1461,32 +1349,12 @@ template <int RES, bool FULL = true> struct MtEngT {
         const int wN0 = winN;
         MT_UB(u0); MT_UC(4, wN0); MT_UC(5, 1);
         if (wN0 <= MT_G_MWMIN) {                    // a few chunks: wave 0 alone, no barriers
-#if MT_G_ALLCH
-            // every chunk's rows in one round trip (one wave per SIMD here: registers to spare),
-            // then placed in order (placement writes only entries below the chunk it places)
-            constexpr int NC = MT_G_MWMIN / MT_WAVE;
-            LaneArr<WinI> wis[NC];
-#pragma unroll
-            for (int q = 0; q < NC; q++) {
-                const int base = q * MT_WAVE;
-                const int m = base >= wN0 ? 0 : ((wN0 - base) < MT_WAVE ? (wN0 - base) : MT_WAVE);
-                const auto ids = wave_map(m, [&](int k) MT_LAM { return winGet(base + k); });
-                wis[q] = wave_map(m, [&](int k) MT_LAM { return winEntry(own(ids, k), r, c); });
-            }
-#pragma unroll
-            for (int q = 0; q < NC; q++) {
-                const int base = q * MT_WAVE;
-                if (base >= wN0) break;
-                placeChunk(wis[q], base, (wN0 - base) < MT_WAVE ? (wN0 - base) : MT_WAVE, prune, newWin);
-            }
-#else
             for (int base = 0; base < wN0; base += MT_WAVE) {
                 const int m = (wN0 - base) < MT_WAVE ? (wN0 - base) : MT_WAVE;
                 const auto ids = wave_map(m, [&](int k) MT_LAM { return winGet(base + k); });
                 const auto wi = wave_map(m, [&](int k) MT_LAM { return winEntry(own(ids, k), r, c); });
                 placeChunk(wi, base, m, prune, newWin);
             }
-#endif
         }
         for (int r0 = 0; wN0 > MT_G_MWMIN && r0 < wN0; r0 += MT_G_STG) {
             const int n = (wN0 - r0) < MT_G_STG ? (wN0 - r0) : MT_G_STG;
@@ -1520,8 +1388,8 @@ template <int RES, bool FULL = true> struct MtEngT {
         int sl = (int)htHash(key);
         won = false;
         for (;;) {
-            const int old = lds_cas(&G.htk[sl], MT_BC_EMPTY, key);
-            if (old == MT_BC_EMPTY) { won = true; break; }
+            const int old = lds_cas(&G.htk[sl], MT_HT_EMPTY, key);
+            if (old == MT_HT_EMPTY) { won = true; break; }
             if (old == key) break;
             sl = (sl + 1) & (MT_G_HT - 1);
         }
@@ -1534,7 +1402,7 @@ template <int RES, bool FULL = true> struct MtEngT {
         for (;;) {
             const int k = G.htk[sl];
             if (k == key) return G.htv[sl];
-            if (k == MT_BC_EMPTY) return 0;
+            if (k == MT_HT_EMPTY) return 0;
             sl = (sl + 1) & (MT_G_HT - 1);
         }
     }
@@ -1553,7 +1421,7 @@ template <int RES, bool FULL = true> struct MtEngT {
         MtLdsBig& G = mt_ldsg();
         for (int base = 0; base < hlistN; base += MT_WAVE) {               // the last U set's slots
             const int m = (hlistN - base) < MT_WAVE ? (hlistN - base) : MT_WAVE;
-            wave_for(m, [&](int k) MT_LAM { const int sl = G.hlist[base + k]; G.htk[sl] = MT_BC_EMPTY; G.htv[sl] = 0; });
+            wave_for(m, [&](int k) MT_LAM { const int sl = G.hlist[base + k]; G.htk[sl] = MT_HT_EMPTY; G.htv[sl] = 0; });
         }
         hlistN = 0;
         wave_sync();
@@ -1573,7 +1441,7 @@ template <int RES, bool FULL = true> struct MtEngT {
             if (hlistN + (l1 - l0) > MT_G_HTN) {
                 for (int base = 0; base < hlistN; base += MT_WAVE) {
                     const int m = (hlistN - base) < MT_WAVE ? (hlistN - base) : MT_WAVE;
-                    wave_for(m, [&](int k) MT_LAM { const int sl = G.hlist[base + k]; G.htk[sl] = MT_BC_EMPTY; G.htv[sl] = 0; });
+                    wave_for(m, [&](int k) MT_LAM { const int sl = G.hlist[base + k]; G.htk[sl] = MT_HT_EMPTY; G.htv[sl] = 0; });
                 }
                 hlistN = 0;
                 wave_sync();
@@ -1627,10 +1495,10 @@ template <int RES, bool FULL = true> struct MtEngT {
             }
             wave_sync();
         }
-        // Window rows, one 64-entry chunk at a time, software-pipelined: chunk i+1's row
-        // fields are in flight while chunk i is processed, and chunk i+2's window ids behind
-        // them (the window entries are distinct rows and compaction only writes entries below
-        // the chunk being read, so the early reads see what in-order reads would).
+        // Window rows, one 64-entry chunk at a time; the next chunk's window ids load behind
+        // this chunk's rows (compaction only writes entries below the chunk being read, so the
+        // early read sees what an in-order read would).  Holding two chunks' rows in flight was
+        // tried and costs the hot kernel spills.
         auto winIds = [&](int base) MT_LAM {
             const int m = (winN - base) < MT_WAVE ? (winN - base) : MT_WAVE;
             return wave_map(m, [&](int k) MT_LAM { return winGet(base + k); });
@@ -1640,33 +1508,12 @@ template <int RES, bool FULL = true> struct MtEngT {
             return wave_map(m, [&](int k) MT_LAM { return winEntry(own(ids, k), r, c); });
         };
         const int wN0 = winN;
-#ifndef MT_CU_PIPE
-#define MT_CU_PIPE 0
-#endif
-#if MT_CU_PIPE
-        LaneArr<WinI> wiNext{};
-        LaneArr<int> idNext{};
-        if (wN0 > 0) wiNext = winRows(winIds(0), 0);
-        if (wN0 > MT_WAVE) idNext = winIds(MT_WAVE);
-#else
         LaneArr<int> idn{};
         if (wN0 > 0) idn = winIds(0);
-#endif
         for (int base = 0; base < wN0; base += MT_WAVE) {
             const int m = (wN0 - base) < MT_WAVE ? (wN0 - base) : MT_WAVE;
-#if MT_CU_PIPE
-            const auto wi = wiNext;
-            if (base + MT_WAVE < wN0) {
-                wiNext = winRows(idNext, base + MT_WAVE);
-                if (base + 2 * MT_WAVE < wN0) idNext = winIds(base + 2 * MT_WAVE);
-            }
-#else
-            // one chunk's rows at a time (the software-pipelined variant, MT_CU_PIPE, holds two
-            // chunks in VGPRs and costs the hot kernel spills); the next chunk's window ids load
-            // behind this chunk's rows
             const auto wi = winRows(idn, base);
             if (base + MT_WAVE < wN0) idn = winIds(base + MT_WAVE);
-#endif
             auto live = wave_map(m, [&](int k) MT_LAM { return own(wi, k).live; });
             if (prune) {
                 auto rk = wave_rank(live);
@@ -1913,7 +1760,6 @@ template <int RES, bool FULL = true> struct MtEngT {
     // round trip.
     MT_HD LaneArr<ChildL> leafLens(const LaneArr<int>& ch, int n, int r, int c, LaneArr<uint32_t>& lm, LaneArr<int>& lp,
                                    LaneArr<int>& lr) {
-#if MT_SCOUR_QUADS
         // each row as three 16-byte loads (len seq rseq meta | toff props parent tcap | ovl rcl mid)
         const auto q0 = wave_map(n, [&](int j) MT_LAM { return ((const MtQ16a*)&row(own(ch, j)))[0]; });
         const auto q1 = wave_map(n, [&](int j) MT_LAM { return ((const MtQ16a*)&row(own(ch, j)))[1]; });
@@ -1928,26 +1774,12 @@ template <int RES, bool FULL = true> struct MtEngT {
             const unsigned long long ovl = (unsigned long long)x.x | ((unsigned long long)x.y << 32);
             ChildL o;
             o.len = vis_rc((int)a.y, mt, rs, x.z, ovl, r, c, ovx, ovxN, own(ch, j)) ? (int)a.x : 0;
-            o.tie = !((mt & MT_M_REMOVED) && rs <= r);     // breakTie (MT/mergeTree.ts:2270-2292)
-            return o;
-        });
-#else
-        lm = wave_map(n, [&](int j) MT_LAM { return row(own(ch, j)).meta; });
-        lp = wave_map(n, [&](int j) MT_LAM { return row(own(ch, j)).props; });
-        lr = wave_map(n, [&](int j) MT_LAM { return row(own(ch, j)).len; });
-        return wave_map(n, [&](int j) MT_LAM {
-            const int s = own(ch, j);
-            const uint32_t mt = own(lm, j);
-            const int rs = row(s).rseq;
-            ChildL o;
-            o.len = vis_rc(row(s).seq, mt, rs, row(s).rcl, row(s).ovl, r, c, ovx, ovxN, s) ? row(s).len : 0;
             // breakTie for a leaf at pos 0 (MT/mergeTree.ts:2270-2292): false if a
             // removal the author has seen (removedSeq <= refSeq); true otherwise
             // (every row has an assigned seq on the replay path).
             o.tie = !((mt & MT_M_REMOVED) && rs <= r);
             return o;
         });
-#endif
     }
     // Perspective lengths of block B's children (nodeLength, MT/mergeTree.ts:1652-1692).
     // lsN >= 0 (MT_RES_BIG descents): only the lsN U entries listed in ulist lie under B.
@@ -2086,27 +1918,8 @@ template <int RES, bool FULL = true> struct MtEngT {
     // Row split (BaseSegment.splitAt MT/mergeTree.ts:538-582; TextSegment
     // createSplitSegmentAt textSegment.ts:103-111): the right half copies every
     // attribute; the property map is immutable here, so both halves share it.
-    MT_HD int splitRow(int s, int pos) {
-        MT_EV2(5, 1);
-        const int n = allocRow();
-        if (n < 0) return -1;
-#if defined(MT_DBG_FAIL) && defined(__HIP_DEVICE_COMPILE__)
-        mt_dbg_v.s = s; mt_dbg_v.n = n; mt_dbg_v.op = curOp;
-#endif
-        const int ls = uni(row(s).len);
-        const uint32_t mt = uni(row(s).meta);
-        row(n).len = ls - pos; row(s).len = pos;
-        const unsigned long long ov = uni64(row(s).ovl);
-        row(n).seq = row(s).seq; row(n).rseq = row(s).rseq; row(n).meta = mt & ~(MT_M_INWIN | MT_M_HREF); row(n).ovl = ov;
-        row(n).rcl = row(s).rcl; row(n).mid = 0;
-        if (ov >> 63) ovxCopy(s, n);
-        row(n).toff = row(s).toff + pos; row(n).props = row(s).props; row(n).parent = row(s).parent;
-        row(n).tcap = row(s).tcap - pos; row(s).tcap = pos;   // each row owns [toff, toff+tcap) of the arena
-        if (mt & MT_M_INWIN) winAddKnown(n, mt & ~(MT_M_INWIN | MT_M_HREF));   // n's meta as just written
-        return n;
-    }
-    // splitRow with row s already loaded (lane j of lf, the walk's leaf step): the right half is
-    // written by twelve lanes in one store (one dword each) and nothing of s is read again.
+    // Row s is already loaded (lane j of lf, the walk's leaf step): lane j writes the right
+    // half whole and nothing of s is read again.
     // dword k of a row held in registers (k a compile-time constant after unrolling: no address
     // is taken, so the record stays in VGPRs)
     MT_HD static int rowDword(const MtRow& f, int k) {
@@ -2117,19 +1930,15 @@ template <int RES, bool FULL = true> struct MtEngT {
             case 10: return (int)f.rcl; default: return f.mid;
         }
     }
-    MT_HD static LaneArr<int> leafField(const LaneArr<MtRow>& lf, int j, int k) {
-        (void)j;
+    MT_HD static LaneArr<int> leafField(const LaneArr<MtRow>& lf, int k) {
         return wave_map(MT_WAVE, [&](int t) MT_LAM { return rowDword(own(lf, t), k); });
     }
-    MT_HD int splitRowKnown(int s, int pos, const LaneArr<MtRow>& lf, int j) {
+    MT_HD int splitRow(int s, int pos, const LaneArr<MtRow>& lf, int j) {
         MT_EV2(5, 1);
         const int n = allocRow();
         if (n < 0) return -1;
-#if defined(MT_DBG_FAIL) && defined(__HIP_DEVICE_COMPILE__)
-        mt_dbg_v.s = s; mt_dbg_v.n = n; mt_dbg_v.op = curOp;
-#endif
-        const uint32_t mt = (uint32_t)wave_at(leafField(lf, j, 3), j);
-        const uint32_t ovh = (uint32_t)wave_at(leafField(lf, j, 9), j);
+        const uint32_t mt = (uint32_t)wave_at(leafField(lf, 3), j);
+        const uint32_t ovh = (uint32_t)wave_at(leafField(lf, 9), j);
         // lane j holds row s: it writes the right half whole (three 16-byte stores)
         wave_for(MT_WAVE, [&](int t) MT_LAM {
             if (t != j) return;
@@ -2201,38 +2010,6 @@ template <int RES, bool FULL = true> struct MtEngT {
             node = NB; idx = uni(sc->pathJ[L - 1]) + 1; L = L - 1;
         }
     }
-#if defined(MT_DBG_FAIL) && defined(__HIP_DEVICE_COMPILE__)
-    // Diagnostic builds only: a walk found no position.  Prints the walk's view of the
-    // block's children beside fresh (volatile, after a full wait) reloads of the same records.
-    __device__ void dbgWalkFail(int kind, int B, const BlkH& h, int ch, const ChildL& cl, int pos, int p, int total, int L,
-                                int r, int c) {
-        __builtin_amdgcn_s_waitcnt(0);
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
-        const int lane = wave_lane();
-        if (lane == 0)
-            printf("WALKFAIL op=%u kind=%d B=%d height=%d n=%d hlen=%d L=%d root=%d H=%d pos=%d p=%d total=%d r=%d c=%d "
-                   "minSeq=%d curSeq=%d uValid=%d nU=%d lastSplit(s=%d n=%d op=%u)\n",
-                   curOp, kind, B, h.height, h.n, h.len, L, root, height, pos, p, total, r, c, minSeq, curSeq, (int)uValid, nU,
-                   mt_dbg_v.s, mt_dbg_v.n, mt_dbg_v.op);
-        if (lane < h.n) {
-            if (h.height == 0) {
-                const volatile MtRow* v = (const volatile MtRow*)&row(ch);
-                const int ln = v->len, sq = v->seq, rs = v->rseq, par = v->parent;
-                const uint32_t mt = v->meta, rc = v->rcl;
-                const unsigned long long ov = v->ovl;
-                const bool vis = vis_rc(sq, mt, rs, rc, ov, r, c, ovx, ovxN, ch);
-                printf("  WALKFAIL child %d row=%d used_len=%d tie=%d | fresh len=%d seq=%d rseq=%d meta=%x rcl=%u ovl=%llx "
-                       "parent=%d vis=%d\n", lane, ch, cl.len, (int)cl.tie, ln, sq, rs, mt, rc, ov, par, (int)vis);
-            } else {
-                int corr = 0;
-                if constexpr (BT) corr = LB().bcorr[ch];
-                const volatile MtBlk* v = (const volatile MtBlk*)&bk(ch);
-                printf("  WALKFAIL child %d blk=%d used_len=%d | bk.len=%d bcorr=%d n=%d parent=%d height=%d\n", lane, ch, cl.len,
-                       v->len, corr, v->n, v->parent, v->height);
-            }
-        }
-    }
-#endif
     // A remove or annotate whose whole range lies in the leaf block B that its start walk has
     // just loaded (MT_RANGE_LEAF): the two boundary splits, the marking of the covered rows,
     // their window entries and the LRU entry are all made here from the rows in registers
@@ -2396,10 +2173,10 @@ template <int RES, bool FULL = true> struct MtEngT {
             LaneArr<int> r0{}, r1{};
             if (kpre) kidsLoad(ch, h.n, r0, r1);
             // Leaf rows: every field in one round trip (MtRow is three 16-byte loads per lane), so a
-            // split that follows needs no second load of the row (splitRowKnown).
+            // split that follows needs no second load of the row (splitRow).
             LaneArr<MtRow> lf{};
             LaneArr<ChildL> cl;
-            if (MT_LEAF_ONCE && h.height == 0) {
+            if (h.height == 0) {
                 const int rr = r, cc = c;
                 lf = wave_map(h.n, [&](int j) MT_LAM { return row(own(ch, j)); });
                 cl = wave_map(h.n, [&](int j) MT_LAM {
@@ -2427,19 +2204,19 @@ template <int RES, bool FULL = true> struct MtEngT {
                 if (interior) {
                     sc->pathJ[L] = j; L++; B = wave_at(ch, j); p = pj;
                     if (narrow && h.height > 1) lsN = narrowU(lsN, h.height - 1, B);
-                    if (kpre) ch = kidRec(r0, r1, j, h, B); else ch = blkLoad(B, h);
+                    if (kpre) ch = kidRec(r0, r1, j, h); else ch = blkLoad(B, h);
                     continue;
                 }
                 const int s = wave_at(ch, j);
                 lastL = L; lastSplit = false;
-                if (MT_RANGE_LEAF && MT_LEAF_ONCE && kind == MT_WALK_RANGE) {
+                if (MT_RANGE_LEAF && kind == MT_WALK_RANGE) {
                     if (rangeLeaf(B, L, h, ch, lf, cl, pre, total, p, j, rEnd - pos, rMode, c, rSq, rOpset, rPm))
                         return MT_W_RANGED;
                 }
                 if (kind != MT_WALK_INSERT) {
-                    const uint32_t sm = MT_LEAF_ONCE ? (uint32_t)wave_at(leafField(lf, j, 3), j) : uni(row(s).meta);
+                    const uint32_t sm = (uint32_t)wave_at(leafField(lf, 3), j);
                     if (pj > 0 && !(sm & MT_M_MARKER)) {
-                        const int n = MT_LEAF_ONCE ? splitRowKnown(s, pj, lf, j) : splitRow(s, pj);
+                        const int n = splitRow(s, pj, lf, j);
                         if (n < 0) return MT_W_FAIL;
                         insertAtPath(L, j + 1, n, 0);
                         if (FULL && drec) {                     // SPLIT, splitLeafSegment (mergeTree.ts:2243-2258)
@@ -2469,9 +2246,6 @@ template <int RES, bool FULL = true> struct MtEngT {
                 uValid = false;
                 return MT_W_OK;
             }
-#if defined(MT_DBG_FAIL) && defined(__HIP_DEVICE_COMPILE__)
-            dbgWalkFail(kind, B, h, ch, cl, pos, p, total, L, r, c);
-#endif
             return MT_W_FAIL;
         }
     }
@@ -2779,7 +2553,6 @@ template <int RES, bool FULL = true> struct MtEngT {
             const int b = own(bsel, t);
             return (t & 7) < bk(b).n ? bk(b).c[t & 7] : -1;
         });
-#if MT_SCOUR_QUADS
         // the fields below are the row's first two quads (len seq rseq meta | toff props parent
         // tcap): two 16-byte loads per lane instead of seven dword loads
         const auto q0 = wave_map(span, [&](int j) MT_LAM {
@@ -2797,15 +2570,6 @@ template <int RES, bool FULL = true> struct MtEngT {
         auto ft = wave_map(span, [&](int j) MT_LAM { return (int)own(q1, j).x; });
         auto fp = wave_map(span, [&](int j) MT_LAM { return (int)own(q1, j).y; });
         auto fc = wave_map(span, [&](int j) MT_LAM { return (int)own(q1, j).w; });
-#else
-        auto fm = wave_map(span, [&](int j) MT_LAM { const int g = own(f, j); return g >= 0 ? (int)row(g).meta : 0; });
-        auto fs = wave_map(span, [&](int j) MT_LAM { const int g = own(f, j); return g >= 0 ? row(g).seq : 0; });
-        auto fr = wave_map(span, [&](int j) MT_LAM { const int g = own(f, j); return g >= 0 ? row(g).rseq : 0; });
-        auto fl = wave_map(span, [&](int j) MT_LAM { const int g = own(f, j); return g >= 0 ? row(g).len : 0; });
-        auto fp = wave_map(span, [&](int j) MT_LAM { const int g = own(f, j); return g >= 0 ? row(g).props : 0; });
-        auto ft = wave_map(span, [&](int j) MT_LAM { const int g = own(f, j); return g >= 0 ? row(g).toff : 0; });
-        auto fc = wave_map(span, [&](int j) MT_LAM { const int g = own(f, j); return g >= 0 ? row(g).tcap : 0; });
-#endif
         const int ms = minSeq;
         // class: 0 empty, 1 unlink, 2 held removed, 3 held above the MSN, 4 candidate
         auto cls = wave_map(span, [&](int t) MT_LAM {
@@ -3609,7 +3373,7 @@ template <int RES, bool FULL = true> struct MtEngT {
             const int n = allocRow();
             if (n < 0) return;
             // payloads up to 64 units are already in lanes: flag text without a newline
-            const bool nonl = MT_NONL && !marker && plen <= MT_WAVE &&
+            const bool nonl = !marker && plen <= MT_WAVE &&
                               wave_count(wave_map(plen, [&](int k) MT_LAM { return own(pay, k) == (int)'\n'; })) == 0;
             const uint32_t m0 = (uint32_t)c | (marker ? MT_M_MARKER : 0u) | (nonl ? MT_M_NONL : 0u);
             row(n).len = L; row(n).seq = sq; row(n).rseq = MT_NOREM;
@@ -3806,7 +3570,7 @@ template <int RES, bool FULL = true> struct MtEngT {
         // (A start past the perspective length fails at the root and leaves the path of an
         // earlier walk behind: then both walks start at the root.)
         int L0 = 0;
-        if (MT_PATH_RESUME && w != MT_W_FAIL && !lastSplit && uValid && uRef == r && uCli == c) {
+        if (w != MT_W_FAIL && !lastSplit && uValid && uRef == r && uCli == c) {
             for (int l = lastL; l > 0; l--) {
                 if (end - uni(sc->pathOff[l]) <= uni(sc->pathLen[l])) { L0 = l; break; }
             }

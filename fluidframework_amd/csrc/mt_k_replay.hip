@@ -54,10 +54,10 @@ __global__ __launch_bounds__(64, 2) void mt_replay_blkw_kernel(MtState S, MtOps 
     const uint32_t cur = mt_replay_doc<MT_RES_BLKW, FULL, CONT>(S, ops, run, &sc, 0, MT_BW_BLKS, MT_BW_HEAP);
     if (__lane_id() == 0) cursor[run] = cur;
 }
-// Long documents (MT_RES_BIG): heap, window, U set and a block cache of the tree's upper
-// levels in LDS (~137 KB, one workgroup per CU), rows and the other blocks in HBM; one wave
-// per SIMD at most, so the register budget is 256 VGPRs.  A document whose heap or height
-// outgrows LDS continues in HBM.  lb < 0: block cache off.
+// Long documents (MT_RES_BIG): heap, window, U set, corrections table and parent cache in
+// LDS (one workgroup per CU), rows and blocks in HBM; one wave per SIMD at most, so the
+// register budget is 256 VGPRs.  A document whose heap or height outgrows LDS continues in
+// HBM.  lb: MT_BIGF_* switches.
 // A workgroup of MT_G_NW waves per document: wave 0 replays, the others serve its posted
 // computeU shares (MtEngT::mwRun / mwShare) until it posts MT_MW_EXIT; every wave reaches
 // the same barriers, and wave 0 posts the exit on every path.

@@ -459,8 +459,8 @@ int  mt_apply_batch_parts(mt_ctx* ctx, uint32_t n_parts, const mt_op_batch* part
  * documents (blocks beyond LDS): zamboni heap, collab window, U set, per-block
  * corrections table and parent cache in LDS (one four-wave workgroup per CU),
  * blocks/rows/text in HBM, same in-wave hand-over (rows = window entries kept in
- * LDS, the rest stay in HBM; blocks = A/B switches, bits 1 block cache, 2 zamboni
- * prefetch, 4 corrections table, 8 parent cache: off).
+ * LDS, the rest stay in HBM; blocks = A/B switches, bits 2 zamboni prefetch,
+ * 4 corrections table, 8 parent cache: off; bit 1 is reserved and has no effect).
  * rows/blocks/heap (0 = compiled maximum) may only lower the caps; tests use
  * small caps to force the hand-over. */
 int  mt_set_residency(mt_ctx* ctx, int use_lds, int rows, int blocks, int heap);
