@@ -59,13 +59,6 @@ const char* MT_FN(last_error)(mt_ctx* c) { return c ? c->err.c_str() : "null con
 __attribute__((used)) const char MT_FN(source_hash_tag)[] = "mt-src-hash:" MT_SRC_HASH;
 const char* MT_FN(source_hash)(void) { return MT_FN(source_hash_tag) + 12; }
 
-// Bytes of the pools allocated for `t` elements each and D documents.
-static uint64_t mt_pool_bytes_of(const MtDocLayout& t, size_t D) {
-    return sizeof(MtRow) * t.row + sizeof(MtBlk) * t.blk + sizeof(MtHeapE) * t.heap + 12ull * t.win + 4ull * t.anc +
-           2ull * t.text + sizeof(MtPSet) * t.pset +
-           (sizeof(MtDocHdr) + 4ull * MT_RFL + sizeof(MtDocLayout) + sizeof(MtOvx) * MT_OVX_CAP + sizeof(MtReg) * MT_REG_CAP) * D +
-           4ull * t.mid + 4ull * t.regr;
-}
 // Pools of every document, laid out back to back with per-document capacities.
 static void mt_caps_default(mt_limits& q) {
     if (!q.rows_per_doc) q.rows_per_doc = 4096;
@@ -77,6 +70,13 @@ static void mt_caps_default(mt_limits& q) {
     if (!q.markers_per_doc) q.markers_per_doc = 1024;
     if (!q.register_rows_per_doc) q.register_rows_per_doc = 256;
 }
+static bool mt_caps_too_large(mt_ctx* c, const MtDocLayout& y) {
+    for (const MtCapDesc& k : MT_CAPS)
+        if (y.*k.cap > k.max) { c->err = "per-document capacity too large"; return true; }
+    return false;
+}
+static int mt_rederive(mt_ctx* c);
+static int mt_delta_size(mt_ctx* c, uint64_t capacity);
 static int mt_create_impl(int device, uint32_t n_docs, const mt_limits* caps, bool uniform, mt_ctx** out) {
     mt_ctx* c = new mt_ctx();
     *out = c;
@@ -90,41 +90,22 @@ static int mt_create_impl(int device, uint32_t n_docs, const mt_limits* caps, bo
     for (uint32_t d = 0; d < n_docs; d++) {
         mt_limits q = caps[uniform ? 0 : d];
         mt_caps_default(q);
-        if (q.rows_per_doc > (1u << 30) || q.text_per_doc > (1u << 30) || q.window_per_doc > (1u << 26) ||
-            q.register_rows_per_doc > (1u << 24)) {
-            c->err = "per-document capacity too large"; return MT_E_INVALID;
-        }
         MtDocLayout& y = c->layout_h[d];
-        y.row = tot.row; y.blk = tot.blk; y.heap = tot.heap; y.win = tot.win; y.anc = tot.anc; y.text = tot.text; y.pset = tot.pset;
-        y.mid = tot.mid; y.regr = tot.regr;
-        y.rowCap = q.rows_per_doc; y.blkCap = q.blocks_per_doc; y.heapCap = q.heap_per_doc; y.winCap = q.window_per_doc;
-        y.textCap = q.text_per_doc; y.psetCap = q.propsets_per_doc; y.midCap = q.markers_per_doc;
-        y.regCap = q.register_rows_per_doc;
-        tot.row += y.rowCap; tot.blk += y.blkCap; tot.heap += y.heapCap + 1; tot.win += y.winCap;
-        tot.anc += (unsigned long long)y.winCap * MT_MAXH; tot.text += 2ull * y.textCap; tot.pset += y.psetCap;
-        tot.mid += y.midCap; tot.regr += 2ull * y.regCap;
-        S.rowCap = std::max(S.rowCap, y.rowCap); S.blkCap = std::max(S.blkCap, y.blkCap); S.heapCap = std::max(S.heapCap, y.heapCap);
-        S.winCap = std::max(S.winCap, y.winCap); S.textCap = std::max(S.textCap, y.textCap); S.psetCap = std::max(S.psetCap, y.psetCap);
+        for (const MtCapDesc& k : MT_CAPS) y.*k.cap = q.*k.lim;
+        if (mt_caps_too_large(c, y)) return MT_E_INVALID;
+        const MtDocLayout s = mt_slice(y);
+        for (auto f : MT_LY_OFF) { y.*f = tot.*f; tot.*f += s.*f; }
     }
     const size_t D = S.maxDocs;
-    void* p;
-#define MT_ALLOC(field, T, count) \
-    if (mtb_malloc(&p, sizeof(T) * (size_t)(count)) != 0) { c->err = "pool allocation failed: " #field; return MT_E_OOM; } \
-    S.field = (T*)p;
-    MT_ALLOC(rows, MtRow, tot.row)
-    MT_ALLOC(blk, MtBlk, tot.blk) MT_ALLOC(heap, MtHeapE, tot.heap) MT_ALLOC(win, int, tot.win)
-    MT_ALLOC(uid, int, tot.win) MT_ALLOC(udelta, int, tot.win) MT_ALLOC(uanc, int, tot.anc)
-    MT_ALLOC(text, uint16_t, tot.text) MT_ALLOC(pset, MtPSet, tot.pset) MT_ALLOC(hdr, MtDocHdr, D)
-    MT_ALLOC(hold, int, D * MT_RFL) MT_ALLOC(ovx, MtOvx, D * MT_OVX_CAP) MT_ALLOC(mid, int, tot.mid)
-    MT_ALLOC(reg, MtReg, D * MT_REG_CAP) MT_ALLOC(regr, int, tot.regr)
-#undef MT_ALLOC
-    if (mtb_malloc(&p, sizeof(MtDocLayout) * D) != 0) { c->err = "pool allocation failed: layout"; return MT_E_OOM; }
-    S.layout = (const MtDocLayout*)p;
-    mtb_h2d(c, p, c->layout_h.data(), sizeof(MtDocLayout) * D);
+    for (const MtPoolDesc& d : MT_POOLS) {
+        void* p;
+        if (mtb_malloc(&p, mt_pool_bytes(d, tot, D)) != 0) { c->err = std::string("pool allocation failed: ") + d.field; return MT_E_OOM; }
+        mt_pool_set(S, d, p);
+    }
+    mtb_h2d(c, (void*)S.layout, c->layout_h.data(), sizeof(MtDocLayout) * D);
     mtb_memset(S.hdr, 0, sizeof(MtDocHdr) * D);
     c->tot = tot; c->cap = tot;
-    c->pool_bytes = mt_pool_bytes_of(tot, D);
-    return MT_OK;
+    return mt_rederive(c);
 }
 
 int MT_FN(create)(int device, const mt_limits* L, mt_ctx** out) {
@@ -139,18 +120,6 @@ int MT_FN(create_docs)(int device, uint32_t n_docs, const mt_limits* per_doc, mt
 // text, property sets, headers, recycled-row stacks): the engine's equivalent of
 // a summary to resume from (SURVEY.md §5 checkpoint/resume), used by benchmarks
 // that replay the same stream on the same starting state.
-struct MtCkPart { void** ck; void* live; size_t bytes; };
-static std::vector<MtCkPart> mt_ck_parts(mt_ctx* c, const MtDocLayout& t) {
-    const MtState& S = c->S; const size_t D = S.maxDocs;
-    return {{&c->ck_rows, S.rows, sizeof(MtRow) * t.row}, {&c->ck_blk, S.blk, sizeof(MtBlk) * t.blk},
-            {&c->ck_heap, S.heap, sizeof(MtHeapE) * t.heap}, {&c->ck_win, S.win, 4ull * t.win},
-            {&c->ck_text, S.text, 2ull * t.text}, {&c->ck_pset, S.pset, sizeof(MtPSet) * t.pset},
-            {&c->ck_hdr, S.hdr, sizeof(MtDocHdr) * D}, {&c->ck_hold, S.hold, 4ull * MT_RFL * D},
-            {&c->ck_ovx, S.ovx, sizeof(MtOvx) * MT_OVX_CAP * D}, {&c->ck_mid, S.mid, 4ull * t.mid},
-            {&c->ck_reg, S.reg, sizeof(MtReg) * MT_REG_CAP * D}, {&c->ck_regr, S.regr, 4ull * t.regr}};
-}
-static int mt_rederive(mt_ctx* c);
-static int mt_delta_size(mt_ctx* c, uint64_t capacity);
 // The pools up to their tails (documents relocated since the last checkpoint may have moved
 // them: the shadows grow with them), and the host's layout beside them.
 int MT_FN(checkpoint)(mt_ctx* c) {
@@ -158,16 +127,15 @@ int MT_FN(checkpoint)(mt_ctx* c) {
     int rc = mtb_sync(c);
     if (rc) return rc;
     c->ck_valid = false;
-    size_t k = 0;
-    for (auto& p : mt_ck_parts(c, c->tot)) {
-        const size_t want = p.bytes ? p.bytes : 16;
-        if (*p.ck && c->ck_bytes[k] < want) { mtb_free(*p.ck); *p.ck = nullptr; c->ck_bytes[k] = 0; }
-        if (!*p.ck) {
-            if (mtb_malloc(p.ck, want) != 0) { *p.ck = nullptr; c->err = "checkpoint allocation failed"; return MT_E_OOM; }
+    for (size_t k = 0; k < MT_NPOOLS; k++) {
+        if (!MT_POOLS[k].ck) continue;
+        const size_t bytes = mt_pool_bytes(MT_POOLS[k], c->tot, c->S.maxDocs), want = bytes ? bytes : 16;
+        if (c->ck[k] && c->ck_bytes[k] < want) { mtb_free(c->ck[k]); c->ck[k] = nullptr; c->ck_bytes[k] = 0; }
+        if (!c->ck[k]) {
+            if (mtb_malloc(&c->ck[k], want) != 0) { c->ck[k] = nullptr; c->err = "checkpoint allocation failed"; return MT_E_OOM; }
             c->ck_bytes[k] = want;
         }
-        if (p.bytes) mtb_d2d(c, *p.ck, p.live, p.bytes);
-        k++;
+        if (bytes) mtb_d2d(c, c->ck[k], mt_pool_get(c->S, MT_POOLS[k]), bytes);
     }
     c->ck_layout = c->layout_h; c->ck_tot = c->tot; c->ck_dead = c->dead;
     c->ck_valid = true;
@@ -179,7 +147,10 @@ int MT_FN(restore)(mt_ctx* c) {
     if (!c || !c->ck_valid) return MT_E_INVALID;
     int rc = mtb_sync(c);
     if (rc) return rc;
-    for (auto& p : mt_ck_parts(c, c->ck_tot)) if (p.bytes) mtb_d2d(c, p.live, *p.ck, p.bytes);
+    for (size_t k = 0; k < MT_NPOOLS; k++) {
+        const size_t bytes = MT_POOLS[k].ck ? mt_pool_bytes(MT_POOLS[k], c->ck_tot, c->S.maxDocs) : 0;
+        if (bytes) mtb_d2d(c, mt_pool_get(c->S, MT_POOLS[k]), c->ck[k], bytes);
+    }
     if (c->layout_h.size() == c->ck_layout.size() &&
         memcmp(c->layout_h.data(), c->ck_layout.data(), sizeof(MtDocLayout) * c->layout_h.size()) != 0) {
         c->layout_h = c->ck_layout;
@@ -208,43 +179,13 @@ static int mtb_launch_relocate(mt_ctx* c, const uint32_t* docs, const MtDocLayou
     return MT_OK;
 }
 #endif
-// The per-document pools: element size and the MtDocLayout field that counts its elements
-// (uid and udelta are laid out as the window is).
-struct MtPoolDesc { void* p; size_t esz; unsigned long long MtDocLayout::*n; const char* name; };
-static std::vector<MtPoolDesc> mt_pools(mt_ctx* c) {
-    const MtState& S = c->S;
-    return {{S.rows, sizeof(MtRow), &MtDocLayout::row, "rows"}, {S.blk, sizeof(MtBlk), &MtDocLayout::blk, "blocks"},
-            {S.heap, sizeof(MtHeapE), &MtDocLayout::heap, "heap"}, {S.win, 4, &MtDocLayout::win, "window"},
-            {S.uid, 4, &MtDocLayout::win, "window"}, {S.udelta, 4, &MtDocLayout::win, "window"},
-            {S.uanc, 4, &MtDocLayout::anc, "window"}, {S.text, 2, &MtDocLayout::text, "text"},
-            {S.pset, sizeof(MtPSet), &MtDocLayout::pset, "property sets"}, {S.mid, 4, &MtDocLayout::mid, "markers"},
-            {S.regr, 4, &MtDocLayout::regr, "register rows"}};
-}
-static void mt_set_pools(mt_ctx* c, const std::vector<MtPoolDesc>& P) {
-    MtState& S = c->S;
-    S.rows = (MtRow*)P[0].p; S.blk = (MtBlk*)P[1].p; S.heap = (MtHeapE*)P[2].p; S.win = (int*)P[3].p; S.uid = (int*)P[4].p;
-    S.udelta = (int*)P[5].p; S.uanc = (int*)P[6].p; S.text = (uint16_t*)P[7].p; S.pset = (MtPSet*)P[8].p; S.mid = (int*)P[9].p;
-    S.regr = (int*)P[10].p;
-}
-static unsigned long long MtDocLayout::*const MT_LY_OFF[9] = {&MtDocLayout::row, &MtDocLayout::blk, &MtDocLayout::heap,
-    &MtDocLayout::win, &MtDocLayout::anc, &MtDocLayout::text, &MtDocLayout::pset, &MtDocLayout::mid, &MtDocLayout::regr};
-// Elements a document of capacities y takes of each pool (in the offset fields).
-static MtDocLayout mt_slice(const MtDocLayout& y) {
-    MtDocLayout s{};
-    s.row = y.rowCap; s.blk = y.blkCap; s.heap = (unsigned long long)y.heapCap + 1; s.win = y.winCap;
-    s.anc = (unsigned long long)y.winCap * MT_MAXH; s.text = 2ull * y.textCap; s.pset = y.psetCap; s.mid = y.midCap;
-    s.regr = 2ull * y.regCap;
-    return s;
-}
 // Everything the library derives from the documents' capacities: the per-pool maxima, the
 // pools' bytes and the capture buffers' minimum sizes (staging sizes are taken per call).
 static int mt_rederive(mt_ctx* c) {
     MtState& S = c->S;
-    S.rowCap = S.blkCap = S.heapCap = S.winCap = S.textCap = S.psetCap = 0;
-    for (const MtDocLayout& y : c->layout_h) {
-        S.rowCap = std::max(S.rowCap, y.rowCap); S.blkCap = std::max(S.blkCap, y.blkCap); S.heapCap = std::max(S.heapCap, y.heapCap);
-        S.winCap = std::max(S.winCap, y.winCap); S.textCap = std::max(S.textCap, y.textCap); S.psetCap = std::max(S.psetCap, y.psetCap);
-    }
+    for (const MtCapDesc& k : MT_CAPS) if (k.most) S.*k.most = 0;
+    for (const MtDocLayout& y : c->layout_h)
+        for (const MtCapDesc& k : MT_CAPS) if (k.most) S.*k.most = std::max(S.*k.most, y.*k.cap);
     c->pool_bytes = mt_pool_bytes_of(c->cap, S.maxDocs);
     return c->delta_req ? mt_delta_size(c, c->delta_req) : MT_OK;
 }
@@ -284,24 +225,13 @@ static int mt_resize_impl(mt_ctx* c, uint32_t n, const uint32_t* docs, const mt_
         const MtDocLayout& y = c->layout_h[docs[i]];
         const mt_limits& q = caps[i];
         MtDocLayout& z = ny[i];
-        z.rowCap = q.rows_per_doc ? q.rows_per_doc : y.rowCap; z.blkCap = q.blocks_per_doc ? q.blocks_per_doc : y.blkCap;
-        z.textCap = q.text_per_doc ? q.text_per_doc : y.textCap; z.psetCap = q.propsets_per_doc ? q.propsets_per_doc : y.psetCap;
-        z.heapCap = q.heap_per_doc ? q.heap_per_doc : y.heapCap; z.winCap = q.window_per_doc ? q.window_per_doc : y.winCap;
-        z.midCap = q.markers_per_doc ? q.markers_per_doc : y.midCap;
-        z.regCap = q.register_rows_per_doc ? q.register_rows_per_doc : y.regCap;
-        if (z.rowCap > (1u << 30) || z.textCap > (1u << 30) || z.winCap > (1u << 26) || z.regCap > (1u << 24) ||
-            z.blkCap > (1u << 30) || z.heapCap > (1u << 30) || z.psetCap > (1u << 30) || z.midCap > (1u << 30)) {
-            c->err = "per-document capacity too large"; return MT_E_INVALID;
-        }
+        for (const MtCapDesc& k : MT_CAPS) z.*k.cap = q.*k.lim ? q.*k.lim : y.*k.cap;
+        if (mt_caps_too_large(c, z)) return MT_E_INVALID;
         const MtOcc& o = occ[i];
-        const struct { const char* pool; uint32_t have, cap; } chk[8] = {
-            {"rows", o.rows, z.rowCap}, {"blocks", o.blks, z.blkCap}, {"text", o.text, z.textCap},
-            {"property sets", o.psets, z.psetCap}, {"heap", o.heap, z.heapCap}, {"window", o.win, z.winCap},
-            {"markers", o.mids, z.midCap}, {"register rows", o.regs, z.regCap}};
-        for (const auto& k : chk)
-            if (k.cap < k.have) {
+        for (const MtCapDesc& k : MT_CAPS)
+            if (z.*k.cap < o.*k.occ) {
                 char b[160];
-                snprintf(b, sizeof b, "document %u: %s capacity %u is below what it holds (%u)", docs[i], k.pool, k.cap, k.have);
+                snprintf(b, sizeof b, "document %u: %s capacity %u is below what it holds (%u)", docs[i], k.name, z.*k.cap, o.*k.occ);
                 c->err = b;
                 return MT_E_INVALID;
             }
@@ -323,10 +253,12 @@ static int mt_resize_impl(mt_ctx* c, uint32_t n, const uint32_t* docs, const mt_
             if (s.*f == s0.*f) z.*f = y.*f;
             else { z.*f = nt.*f; nt.*f += s.*f; }
         }
-        moved += (z.row != y.row ? sizeof(MtRow) * (uint64_t)o.rows : 0) + (z.blk != y.blk ? sizeof(MtBlk) * (uint64_t)o.blks : 0) +
-                 (z.text != y.text ? 2ull * o.text : 0) + (z.pset != y.pset ? sizeof(MtPSet) * (uint64_t)o.psets : 0) +
-                 (z.heap != y.heap ? sizeof(MtHeapE) * ((uint64_t)o.heap + 1) : 0) + (z.win != y.win ? 4ull * o.win : 0) +
-                 (z.mid != y.mid ? 4ull * std::min(y.midCap, z.midCap) : 0) + (z.regr != y.regr ? 4ull * o.regs : 0);
+        // what moves: the holdings (the heap's entry 0 with them; the marker table whole)
+        for (const MtCapDesc& k : MT_CAPS) {
+            if (z.*k.off == y.*k.off) continue;
+            const uint64_t held = k.off == &MtDocLayout::mid ? std::min(y.midCap, z.midCap) : (uint64_t)(o.*k.occ) + (k.off == &MtDocLayout::heap);
+            moved += k.esz * held;
+        }
     }
     // room: every pool whose tail would pass its allocation goes to twice its size or more
     MtDocLayout ncap = c->cap;
@@ -338,26 +270,26 @@ static int mt_resize_impl(mt_ctx* c, uint32_t n, const uint32_t* docs, const mt_
             c->err = "growing the pools would pass the budget (mt_set_autogrow max_pool_bytes)";
             return MT_E_OOM;
         }
-        std::vector<MtPoolDesc> P = mt_pools(c);
-        std::vector<void*> np(P.size(), nullptr);
-        for (size_t k = 0; k < P.size(); k++) {
-            if (ncap.*(P[k].n) == c->cap.*(P[k].n)) continue;
-            const size_t bytes = P[k].esz * (size_t)(ncap.*(P[k].n));
+        void* np[MT_NPOOLS] = {nullptr};
+        for (size_t k = 0; k < MT_NPOOLS; k++) {
+            const MtPoolDesc& d = MT_POOLS[k];
+            if (!d.n || ncap.*d.n == c->cap.*d.n) continue;
+            const size_t bytes = mt_pool_bytes(d, ncap, D);
             if (mtb_malloc(&np[k], bytes ? bytes : 16) != 0) {
                 for (void* q : np) if (q) mtb_free(q);
-                c->err = std::string("pool reallocation failed: ") + P[k].name;
+                c->err = std::string("pool reallocation failed: ") + d.name;
                 return MT_E_OOM;
             }
         }
-        for (size_t k = 0; k < P.size(); k++) {
+        for (size_t k = 0; k < MT_NPOOLS; k++) {
             if (!np[k]) continue;
-            const size_t used = P[k].esz * (size_t)(c->tot.*(P[k].n));
-            if (used) mtb_d2d(c, np[k], P[k].p, used);
-            mtb_free(P[k].p);
-            P[k].p = np[k];
+            void* old = mt_pool_get(c->S, MT_POOLS[k]);
+            const size_t used = mt_pool_bytes(MT_POOLS[k], c->tot, D);
+            if (used) mtb_d2d(c, np[k], old, used);
+            mtb_free(old);
+            mt_pool_set(c->S, MT_POOLS[k], np[k]);
             c->grow_realloc++;
         }
-        mt_set_pools(c, P);
         c->cap = ncap;
         c->pool_bytes = mt_pool_bytes_of(c->cap, D);
     }
@@ -391,8 +323,7 @@ int MT_FN(doc_caps)(mt_ctx* c, uint32_t n, const uint32_t* docs, mt_limits* out)
         const MtDocLayout& y = c->layout_h[docs[i]];
         mt_limits& q = out[i];
         q.max_docs = c->S.maxDocs;
-        q.rows_per_doc = y.rowCap; q.blocks_per_doc = y.blkCap; q.text_per_doc = y.textCap; q.propsets_per_doc = y.psetCap;
-        q.heap_per_doc = y.heapCap; q.window_per_doc = y.winCap; q.markers_per_doc = y.midCap; q.register_rows_per_doc = y.regCap;
+        for (const MtCapDesc& k : MT_CAPS) q.*k.lim = y.*k.cap;
     }
     return MT_OK;
 }
@@ -407,9 +338,7 @@ int MT_FN(doc_occupancy)(mt_ctx* c, uint32_t n, const uint32_t* docs, mt_limits*
     for (uint32_t i = 0; i < n; i++) {
         mt_limits& q = out[i];
         q.max_docs = c->S.maxDocs;
-        q.rows_per_doc = occ[i].rows; q.blocks_per_doc = occ[i].blks; q.text_per_doc = occ[i].text; q.propsets_per_doc = occ[i].psets;
-        q.heap_per_doc = occ[i].heap; q.window_per_doc = occ[i].win; q.markers_per_doc = occ[i].mids;
-        q.register_rows_per_doc = occ[i].regs;
+        for (const MtCapDesc& k : MT_CAPS) q.*k.lim = occ[i].*k.occ;
     }
     return MT_OK;
 }
@@ -420,12 +349,8 @@ int MT_FN(set_autogrow)(mt_ctx* c, int on, uint64_t max_pool_bytes) {
 }
 int MT_FN(grow_stats)(mt_ctx* c, uint64_t out[6]) {
     if (!c || !out) return MT_E_INVALID;
-    uint64_t dead = 0;
-    {   // vacated slices, in bytes (uid / udelta follow the window)
-        const MtDocLayout& d = c->dead;
-        dead = sizeof(MtRow) * d.row + sizeof(MtBlk) * d.blk + sizeof(MtHeapE) * d.heap + 12ull * d.win + 4ull * d.anc +
-               2ull * d.text + sizeof(MtPSet) * d.pset + 4ull * d.mid + 4ull * d.regr;
-    }
+    uint64_t dead = 0;                               // vacated slices, in bytes
+    for (const MtPoolDesc& d : MT_POOLS) if (d.n) dead += mt_pool_bytes(d, c->dead, 0);
     const uint64_t used = mt_pool_bytes_of(c->tot, c->S.maxDocs);
     out[0] = c->grow_reloc; out[1] = c->grow_realloc; out[2] = c->grow_moved; out[3] = used - dead; out[4] = dead;
     out[5] = c->grow_launches;
@@ -439,11 +364,8 @@ int MT_FN(last_resume)(mt_ctx* c, uint32_t n, uint32_t* out) {
 
 void MT_FN(destroy)(mt_ctx* c) {
     if (!c) return;
-    MtState& S = c->S;
-    void* ps[] = {S.rows, S.blk, S.heap, S.win, S.uid, S.udelta, S.uanc, S.text, S.pset, S.hdr, S.hold, (void*)S.layout,
-                  S.ovx, S.mid, S.reg, c->ck_rows, c->ck_blk, c->ck_heap, c->ck_win, c->ck_text, c->ck_pset, c->ck_hdr,
-                  c->ck_hold, c->ck_ovx, c->ck_mid, c->ck_reg, c->ck_regr, S.regr};
-    for (void* p : ps) if (p) mtb_free(p);
+    for (size_t k = 0; k < MT_NPOOLS; k++)
+        for (void* p : {mt_pool_get(c->S, MT_POOLS[k]), c->ck[k]}) if (p) mtb_free(p);
     for (auto* b : c->dev_bufs()) if (b->p) mtb_free(b->p);
     mtb_fini(c);
     delete c;
@@ -571,27 +493,93 @@ static bool mt_scan_wide(mt_ctx* c, size_t n_runs, DocOf doc, Op0 op0, Op1 op1, 
 // Device-built batches (the generators, the exchange: ops never seen on the host): wide when the
 // property sets together could make a document wide.
 static bool mt_dev_wide(const mt_ctx* c) { return c->props_wide; }
+// Such a batch's arrays (b_doc, b_off, b_rec, b_pay; per-run payload bases in b_pbase): generated
+// and exchanged streams hold no relative positions, and no register ops either.
+static MtOps mt_dev_ops(mt_ctx* c, uint32_t n_runs, uint64_t payload_units, bool pay_base) {
+    MtOps o{};
+    o.doc_ids = (const uint32_t*)c->b_doc.p; o.op_off = (const uint32_t*)c->b_off.p; o.rec = (MtOpRec*)c->b_rec.p;
+    o.payload = (uint16_t*)c->b_pay.p; o.n_runs = n_runs; o.payload_units = payload_units;
+    o.pay_base = pay_base ? (const unsigned long long*)c->b_pbase.p : nullptr;
+    return o;
+}
 
 // The batch's arrays in one device region, one pinned staging copy and one asynchronous H2D
 // (stream-ordered before the replay that follows; no host synchronization): doc ids, op
 // offsets, the op records packed to mt_op_rec, the payload and the relative positions.  The
 // caller's arrays are consumed before this returns.
-static int mt_upload_ops(mt_ctx* c, const mt_op_batch* B) {
-    const size_t N = B->n_ops, R = B->n_runs;
+struct MtStageLayout { size_t o_doc, o_off, o_rec, o_pay, o_rel, total; };
+static MtStageLayout mt_stage_layout(size_t R, size_t N, size_t PU, size_t NR) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_doc = 0, o_off = al(o_doc + 4 * R), o_rec = al(o_off + 4 * (R + 1)),
-                 o_pay = al(o_rec + sizeof(MtOpRec) * N), o_rel = al(o_pay + 2 * (size_t)B->payload_units),
-                 total = al(o_rel + sizeof(MtRelPos) * (size_t)(B->rel ? B->n_rel : 0)) + 256;
     static_assert(sizeof(mt_rel_pos) == sizeof(MtRelPos), "relative position layout");
-    int rc;
-    if ((rc = mtb_ensure(c, c->b_batch, total))) return rc;
-    uint8_t* h = (uint8_t*)mtb_stage_get(c, total);
-    if (!h) { c->err = "pinned staging allocation failed"; return MT_E_OOM; }
-    if (R) memcpy(h + o_doc, B->doc_ids, 4 * R);
-    memcpy(h + o_off, B->op_offsets, 4 * (R + 1));
-    MtOpRec* rec = (MtOpRec*)(h + o_rec);
+    MtStageLayout y{};
+    y.o_off = al(y.o_doc + 4 * R); y.o_rec = al(y.o_off + 4 * (R + 1)); y.o_pay = al(y.o_rec + sizeof(MtOpRec) * N);
+    y.o_rel = al(y.o_pay + 2 * PU); y.total = al(y.o_rel + sizeof(MtRelPos) * NR) + 256;
+    return y;
+}
+// The staged arrays at device region d, as the MtOps members they become.
+static MtOps mt_staged_ops(uint8_t* d, const MtStageLayout& y, size_t R, size_t PU, size_t NR) {
+    MtOps o{};
+    o.doc_ids = (const uint32_t*)(d + y.o_doc); o.op_off = (const uint32_t*)(d + y.o_off); o.rec = (MtOpRec*)(d + y.o_rec);
+    o.payload = (uint16_t*)(d + y.o_pay); o.rel = (const MtRelPos*)(d + y.o_rel);
+    o.n_runs = (uint32_t)R; o.payload_units = PU; o.n_rel = (uint32_t)NR;
+    return o;
+}
+// The one place a batch becomes resident.  `o` carries the device pointers and the counts;
+// run_off is the host's copy of its op offsets (n_runs + 1).  Capture, resume, start and growth
+// headroom are cleared: every launch sets them first (mt_replay_resident, mt_replay_capture;
+// mt_generate_docs launches with them clear).  keep_gen: a host upload leaves gen.enabled (and
+// gen_docs) as they are, as it always did, so mt_generated_to_resident still answers for the
+// last generated stream; a device-built batch disarms the generator.
+static void mt_install_batch(mt_ctx* c, MtOps o, const uint32_t* run_off, bool reg, bool wide, bool keep_gen) {
+    o.drec = nullptr; o.dcount = nullptr; o.dcap = 0; o.dtext = nullptr; o.dtcap = 0;
+    o.resume = nullptr; o.start = nullptr; o.grow_pch = 0;
+    c->ops = o;
+    c->n_runs = o.n_runs;
+    c->run_off.assign(run_off, run_off + o.n_runs + 1); c->batch_gen++;
+    c->batch_reg = reg; c->batch_wide = wide;
+    if (!keep_gen) c->gen.enabled = 0;
+}
+// An upload that failed after the regions of the resident batch may have been freed
+// (mtb_ensure): no batch is resident (mt_replay_resident: MT_E_INVALID), and none generated.
+static int mt_drop_batch(mt_ctx* c, int rc) {
+    c->ops = MtOps{};
+    c->n_runs = 0; c->run_off.clear(); c->batch_gen++;
+    c->batch_reg = c->batch_wide = false;
+    c->gen.enabled = 0; c->gen_docs = 0;
+    return rc;
+}
+// A batch's run list: documents in range, op offsets monotone.
+static int mt_check_runs(mt_ctx* c, uint32_t n_runs, const uint32_t* doc_ids, const uint32_t* op_offsets) {
+    for (uint32_t r = 0; r < n_runs; r++) {
+        if (doc_ids[r] >= c->S.maxDocs) { c->err = "doc id out of range"; return MT_E_INVALID; }
+        if (op_offsets[r] > op_offsets[r + 1]) { c->err = "op_offsets not monotone"; return MT_E_INVALID; }
+    }
+    return MT_OK;
+}
+// What every op of a host batch must satisfy (op i of batch B, its property set as the device
+// will see it): the first violation's message, or null.
+static inline __attribute__((always_inline)) const char* mt_op_rule(const mt_op_batch* B, size_t i, int32_t pid, uint32_t nsets) {
+    const uint8_t ty = B->type[i], fl = B->flags[i];
+    if (ty > MT_OP_PASTE) return "unknown op type";
+    if (ty == MT_OP_INSERT && !(fl & MT_OPF_MARKER) && (uint64_t)B->payload_off[i] + B->payload_len[i] > B->payload_units)
+        return "payload out of range";
+    if (pid >= 0 && (uint32_t)pid >= nsets) return "prop_id out of range (mt_set_props first)";
+    if (pid > 32767) return "more than 32767 property sets";
+    if (B->payload_len[i] > 65535) return "insert longer than 65535 UTF-16 units";
+    if (((fl & MT_OPF_REL1) && (uint32_t)B->pos1[i] >= B->n_rel) || ((fl & MT_OPF_REL2) && (uint32_t)B->pos2[i] >= B->n_rel))
+        return "relative position index out of range";
+    return nullptr;
+}
+static int mt_upload_ops(mt_ctx* c, const mt_op_batch* B) {
+    const size_t N = B->n_ops, R = B->n_runs, PU = (size_t)B->payload_units, NR = B->rel ? B->n_rel : 0;
+    const MtStageLayout y = mt_stage_layout(R, N, PU, NR);
+    if (int rc = mtb_ensure(c, c->b_batch, y.total)) return mt_drop_batch(c, rc);
+    uint8_t* h = (uint8_t*)mtb_stage_get(c, y.total);
+    if (!h) { c->err = "pinned staging allocation failed"; return mt_drop_batch(c, MT_E_OOM); }
+    if (R) memcpy(h + y.o_doc, B->doc_ids, 4 * R);
+    memcpy(h + y.o_off, B->op_offsets, 4 * (R + 1));
+    MtOpRec* rec = (MtOpRec*)(h + y.o_rec);
     uint8_t regT[16] = {0};
-    const size_t PU = (size_t)B->payload_units;
     mt_par_for(N, [&](size_t i0, size_t i1, unsigned t) {
         bool reg = false;
         for (size_t i = i0; i < i1; i++) {
@@ -603,24 +591,17 @@ static int mt_upload_ops(mt_ctx* c, const mt_op_batch* B) {
         }
         // this thread's share of the payload (same split, in units)
         const size_t p0 = N ? PU * i0 / N : 0, p1 = N ? PU * i1 / N : PU;
-        if (p1 > p0) memcpy(h + o_pay + 2 * p0, B->payload + p0, 2 * (p1 - p0));
+        if (p1 > p0) memcpy(h + y.o_pay + 2 * p0, B->payload + p0, 2 * (p1 - p0));
         regT[t] = reg;
     });
-    if (!N && PU) memcpy(h + o_pay, B->payload, 2 * PU);
+    if (!N && PU) memcpy(h + y.o_pay, B->payload, 2 * PU);
     bool reg = false;
     for (int t = 0; t < 16; t++) reg |= regT[t] != 0;
-    if (B->rel && B->n_rel) memcpy(h + o_rel, B->rel, sizeof(MtRelPos) * (size_t)B->n_rel);
-    mtb_stage_send(c, c->b_batch.p, total);
-    uint8_t* d = (uint8_t*)c->b_batch.p;
-    MtOps& o = c->ops;
-    o.doc_ids = (const uint32_t*)(d + o_doc); o.op_off = (const uint32_t*)(d + o_off); o.rec = (MtOpRec*)(d + o_rec);
-    o.payload = (uint16_t*)(d + o_pay); o.n_runs = B->n_runs; o.payload_units = B->payload_units; o.pay_base = nullptr;
-    o.rel = (const MtRelPos*)(d + o_rel); o.n_rel = B->rel ? B->n_rel : 0;
-    c->n_runs = B->n_runs;
-    c->run_off.assign(B->op_offsets, B->op_offsets + R + 1); c->batch_gen++;
-    c->batch_reg = reg;
-    c->batch_wide = mt_scan_wide(c, R, [&](size_t r) { return B->doc_ids[r]; }, [&](size_t r) { return B->op_offsets[r]; },
-                                 [&](size_t r) { return B->op_offsets[r + 1]; }, [&](size_t i) { return B->prop_id[i]; });
+    if (NR) memcpy(h + y.o_rel, B->rel, sizeof(MtRelPos) * NR);
+    mtb_stage_send(c, c->b_batch.p, y.total);
+    const bool wide = mt_scan_wide(c, R, [&](size_t r) { return B->doc_ids[r]; }, [&](size_t r) { return B->op_offsets[r]; },
+                                   [&](size_t r) { return B->op_offsets[r + 1]; }, [&](size_t i) { return B->prop_id[i]; });
+    mt_install_batch(c, mt_staged_ops((uint8_t*)c->b_batch.p, y, R, PU, NR), B->op_offsets, reg, wide, true);
     return MT_OK;
 }
 
@@ -628,27 +609,14 @@ static int mt_check_batch(mt_ctx* c, const mt_op_batch* B) {
     if (!B || !B->op_offsets || (B->n_runs && !B->doc_ids)) { c->err = "null batch arrays"; return MT_E_INVALID; }
     if (B->op_offsets[B->n_runs] != B->n_ops) { c->err = "op_offsets[n_runs] != n_ops"; return MT_E_INVALID; }
     if (B->n_rel && !B->rel) { c->err = "n_rel without rel"; return MT_E_INVALID; }
-    for (uint32_t r = 0; r < B->n_runs; r++) {
-        if (B->doc_ids[r] >= c->S.maxDocs) { c->err = "doc id out of range"; return MT_E_INVALID; }
-        if (B->op_offsets[r] > B->op_offsets[r + 1]) { c->err = "op_offsets not monotone"; return MT_E_INVALID; }
-    }
+    if (int rc = mt_check_runs(c, B->n_runs, B->doc_ids, B->op_offsets)) return rc;
     // per op: the first violation's message (threads check disjoint ranges; the lowest op wins)
     const char* errT[16] = {nullptr};
     size_t errI[16];
     const uint32_t nsets = c->S.p_nsets;
     mt_par_for(B->n_ops, [&](size_t i0, size_t i1, unsigned t) {
-        for (size_t i = i0; i < i1; i++) {
-            const char* e = nullptr;
-            if (B->type[i] > MT_OP_PASTE) e = "unknown op type";
-            else if (B->type[i] == MT_OP_INSERT && !(B->flags[i] & MT_OPF_MARKER) &&
-                     (uint64_t)B->payload_off[i] + B->payload_len[i] > B->payload_units) e = "payload out of range";
-            else if (B->prop_id[i] >= 0 && (uint32_t)B->prop_id[i] >= nsets) e = "prop_id out of range (mt_set_props first)";
-            else if (B->prop_id[i] > 32767) e = "more than 32767 property sets";
-            else if (B->payload_len[i] > 65535) e = "insert longer than 65535 UTF-16 units";
-            else if (((B->flags[i] & MT_OPF_REL1) && (uint32_t)B->pos1[i] >= B->n_rel) ||
-                     ((B->flags[i] & MT_OPF_REL2) && (uint32_t)B->pos2[i] >= B->n_rel)) e = "relative position index out of range";
-            if (e) { errT[t] = e; errI[t] = i; return; }
-        }
+        for (size_t i = i0; i < i1; i++)
+            if (const char* e = mt_op_rule(B, i, B->prop_id[i], nsets)) { errT[t] = e; errI[t] = i; return; }
     });
     const char* e = nullptr; size_t ei = 0;
     for (int t = 0; t < 16; t++) if (errT[t] && (!e || errI[t] < ei)) { e = errT[t]; ei = errI[t]; }
@@ -672,25 +640,19 @@ static int mt_upload_parts(mt_ctx* c, uint32_t P, const mt_op_batch* parts, cons
         const mt_op_batch* B = &parts[p];
         if (!B->op_offsets || (B->n_runs && !B->doc_ids) || B->op_offsets[B->n_runs] != B->n_ops ||
             (B->n_rel && !B->rel) || (B->payload_units && !B->payload)) { c->err = "bad batch part"; return MT_E_INVALID; }
-        for (uint32_t r = 0; r < B->n_runs; r++) {
-            if (B->doc_ids[r] >= c->S.maxDocs) { c->err = "doc id out of range"; return MT_E_INVALID; }
-            if (B->op_offsets[r] > B->op_offsets[r + 1]) { c->err = "op_offsets not monotone"; return MT_E_INVALID; }
-        }
+        if (int rc = mt_check_runs(c, B->n_runs, B->doc_ids, B->op_offsets)) return rc;
         opB[p + 1] = opB[p] + B->n_ops; payB[p + 1] = payB[p] + B->payload_units;
         relB[p + 1] = relB[p] + (B->rel ? B->n_rel : 0); runB[p + 1] = runB[p] + B->n_runs;
     }
     const size_t N = opB[P], R = runB[P], PU = payB[P], NR = relB[P];
     if (N >= (1ull << 32) || R >= (1ull << 32) || PU >= (1ull << 32)) { c->err = "batch parts exceed 32-bit indices"; return MT_E_INVALID; }
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_doc = 0, o_off = al(o_doc + 4 * R), o_rec = al(o_off + 4 * (R + 1)),
-                 o_pay = al(o_rec + sizeof(MtOpRec) * N), o_rel = al(o_pay + 2 * PU),
-                 total = al(o_rel + sizeof(MtRelPos) * NR) + 256;
-    int rc;
-    if ((rc = mtb_ensure(c, c->b_batch, total))) return rc;
-    uint8_t* h = (uint8_t*)mtb_stage_get(c, total);
-    if (!h) { c->err = "pinned staging allocation failed"; return MT_E_OOM; }
-    uint32_t* docs = (uint32_t*)(h + o_doc);
-    uint32_t* off = (uint32_t*)(h + o_off);
+    const MtStageLayout y = mt_stage_layout(R, N, PU, NR);
+    // from here on the resident batch's region may be gone: a failure leaves none resident
+    if (int rc = mtb_ensure(c, c->b_batch, y.total)) return mt_drop_batch(c, rc);
+    uint8_t* h = (uint8_t*)mtb_stage_get(c, y.total);
+    if (!h) { c->err = "pinned staging allocation failed"; return mt_drop_batch(c, MT_E_OOM); }
+    uint32_t* docs = (uint32_t*)(h + y.o_doc);
+    uint32_t* off = (uint32_t*)(h + y.o_off);
     std::vector<uint32_t> runOff(R + 1);
     off[0] = 0; runOff[0] = 0;
     for (uint32_t p = 0; p < P; p++) {
@@ -699,9 +661,9 @@ static int mt_upload_parts(mt_ctx* c, uint32_t P, const mt_op_batch* parts, cons
             docs[runB[p] + r] = B->doc_ids[r];
             off[runB[p] + r + 1] = runOff[runB[p] + r + 1] = (uint32_t)(opB[p] + B->op_offsets[r + 1]);
         }
-        if (B->rel && B->n_rel) memcpy(h + o_rel + sizeof(MtRelPos) * relB[p], B->rel, sizeof(MtRelPos) * B->n_rel);
+        if (B->rel && B->n_rel) memcpy(h + y.o_rel + sizeof(MtRelPos) * relB[p], B->rel, sizeof(MtRelPos) * B->n_rel);
     }
-    MtOpRec* rec = (MtOpRec*)(h + o_rec);
+    MtOpRec* rec = (MtOpRec*)(h + y.o_rec);
     const uint32_t nsets = c->S.p_nsets;
     const char* errT[16] = {nullptr};
     size_t errI[16];
@@ -722,13 +684,7 @@ static int mt_upload_parts(mt_ctx* c, uint32_t P, const mt_op_batch* parts, cons
                 else pid = pmap[p][pid];
             }
             const bool text = ty == MT_OP_INSERT && !(fl & MT_OPF_MARKER);
-            if (ty > MT_OP_PASTE) e = "unknown op type";
-            else if (text && (uint64_t)B->payload_off[j] + B->payload_len[j] > B->payload_units) e = "payload out of range";
-            else if (pid >= 0 && (uint32_t)pid >= nsets) e = "prop_id out of range (mt_set_props first)";
-            else if (pid > 32767) e = "more than 32767 property sets";
-            else if (B->payload_len[j] > 65535) e = "insert longer than 65535 UTF-16 units";
-            else if (((fl & MT_OPF_REL1) && (uint32_t)B->pos1[j] >= B->n_rel) ||
-                     ((fl & MT_OPF_REL2) && (uint32_t)B->pos2[j] >= B->n_rel)) e = "relative position index out of range";
+            if (const char* m = mt_op_rule(B, j, pid, nsets)) e = m;
             if (e && !errT[t]) { errT[t] = e; errI[t] = i; }
             o.type = ty; o.flags = fl; o.client = B->client[j]; o.seq = B->seq[j]; o.ref_seq = B->ref_seq[j]; o.msn = B->msn[j];
             o.pos1 = B->pos1[j] + ((fl & MT_OPF_REL1) ? (int32_t)relB[p] : 0);
@@ -741,24 +697,17 @@ static int mt_upload_parts(mt_ctx* c, uint32_t P, const mt_op_batch* parts, cons
     });
     const char* e = nullptr; size_t ei = 0;
     for (int t = 0; t < 16; t++) if (errT[t] && (!e || errI[t] < ei)) { e = errT[t]; ei = errI[t]; }
-    if (e) { c->err = e; return MT_E_INVALID; }
+    if (e) { c->err = e; return mt_drop_batch(c, MT_E_INVALID); }
     mt_par_for(P, [&](size_t p0, size_t p1, unsigned) {           // payloads, part by part
         for (size_t p = p0; p < p1; p++)
-            if (parts[p].payload_units) memcpy(h + o_pay + 2 * payB[p], parts[p].payload, 2 * parts[p].payload_units);
+            if (parts[p].payload_units) memcpy(h + y.o_pay + 2 * payB[p], parts[p].payload, 2 * parts[p].payload_units);
     });
     bool reg = false;
     for (int t = 0; t < 16; t++) reg |= regT[t] != 0;
-    mtb_stage_send(c, c->b_batch.p, total);
-    uint8_t* d = (uint8_t*)c->b_batch.p;
-    MtOps& o = c->ops;
-    o.doc_ids = (const uint32_t*)(d + o_doc); o.op_off = (const uint32_t*)(d + o_off); o.rec = (MtOpRec*)(d + o_rec);
-    o.payload = (uint16_t*)(d + o_pay); o.n_runs = (uint32_t)R; o.payload_units = PU; o.pay_base = nullptr;
-    o.rel = (const MtRelPos*)(d + o_rel); o.n_rel = (uint32_t)NR;
-    c->n_runs = (uint32_t)R;
-    c->run_off.swap(runOff); c->batch_gen++;
-    c->batch_reg = reg;
-    c->batch_wide = mt_scan_wide(c, R, [&](size_t r) { return docs[r]; }, [&](size_t r) { return (size_t)c->run_off[r]; },
-                                 [&](size_t r) { return (size_t)c->run_off[r + 1]; }, [&](size_t i) { return (int)rec[i].prop_id; });
+    mtb_stage_send(c, c->b_batch.p, y.total);
+    const bool wide = mt_scan_wide(c, R, [&](size_t r) { return docs[r]; }, [&](size_t r) { return (size_t)runOff[r]; },
+                                   [&](size_t r) { return (size_t)runOff[r + 1]; }, [&](size_t i) { return (int)rec[i].prop_id; });
+    mt_install_batch(c, mt_staged_ops((uint8_t*)c->b_batch.p, y, R, PU, NR), runOff.data(), reg, wide, true);
     return MT_OK;
 }
 int MT_FN(upload_batch_parts)(mt_ctx* c, uint32_t n_parts, const mt_op_batch* parts, const int32_t* const* prop_map,
@@ -862,18 +811,12 @@ static int mt_replay_capture(mt_ctx* c, const MtGen& g) {
                     return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(nd1, twice), 0x7FFFFFFFull);
                 };
                 mt_limits q{};
-                q.rows_per_doc = up(nd[MT_GROW_ROWS], y.rowCap); q.blocks_per_doc = up(nd[MT_GROW_BLKS], y.blkCap);
-                q.heap_per_doc = up(nd[MT_GROW_HEAP], y.heapCap); q.window_per_doc = up(nd[MT_GROW_WIN], y.winCap);
-                q.text_per_doc = up(nd[MT_GROW_TEXT], y.textCap); q.propsets_per_doc = up(nd[MT_GROW_PSET], y.psetCap);
+                for (const MtCapDesc& k : MT_CAPS) if (k.grow >= 0) q.*k.lim = up(nd[k.grow], y.*k.cap);
                 size_t at = 0;
                 while (at < ids.size() && ids[at] != docs[r]) at++;
                 if (at == ids.size()) { ids.push_back(docs[r]); want.push_back(q); }
-                else {   // (two runs of one document: the larger of each)
-                    mt_limits& w = want[at];
-                    w.rows_per_doc = std::max(w.rows_per_doc, q.rows_per_doc); w.blocks_per_doc = std::max(w.blocks_per_doc, q.blocks_per_doc);
-                    w.heap_per_doc = std::max(w.heap_per_doc, q.heap_per_doc); w.window_per_doc = std::max(w.window_per_doc, q.window_per_doc);
-                    w.text_per_doc = std::max(w.text_per_doc, q.text_per_doc); w.propsets_per_doc = std::max(w.propsets_per_doc, q.propsets_per_doc);
-                }
+                else   // (two runs of one document: the larger of each)
+                    for (const MtCapDesc& k : MT_CAPS) want[at].*k.lim = std::max(want[at].*k.lim, q.*k.lim);
             }
             if (stuck) { c->err = "a document grown to what its next op asked for is short again"; rc = MT_E_OOM; break; }
             if (!ids.empty()) {
@@ -1615,23 +1558,15 @@ int MT_FN(generate_docs)(mt_ctx* c, const mt_gen_params* P, const uint32_t* ops_
     if ((uint64_t)N * P->ins_len_max >= 0xFFFFFFFFull) { c->err = "payload arena exceeds 2^32 units"; return MT_E_INVALID; }
     const size_t PU = N * P->ins_len_max + 1;
     int rc;
-#define AL(buf, bytes) if ((rc = mtb_ensure(c, c->buf, (bytes)))) return rc;
+#define AL(buf, bytes) if ((rc = mtb_ensure(c, c->buf, (bytes)))) return mt_drop_batch(c, rc);
     AL(b_doc, 4ull * P->n_docs) AL(b_off, 4ull * (P->n_docs + 1)) AL(b_rec, sizeof(MtOpRec) * (N + 1)) AL(b_pay, 2 * PU)
     AL(b_gencl, 4ull * P->n_docs)
 #undef AL
     mtb_h2d(c, c->b_doc.p, docs.data(), 4ull * P->n_docs);
     mtb_h2d(c, c->b_off.p, off.data(), 4ull * (P->n_docs + 1));
     mtb_h2d(c, c->b_gencl.p, cl.data(), 4ull * P->n_docs);
-    MtOps& o = c->ops;
-    o.doc_ids = (const uint32_t*)c->b_doc.p; o.op_off = (const uint32_t*)c->b_off.p; o.rec = (MtOpRec*)c->b_rec.p;
-    o.payload = (uint16_t*)c->b_pay.p; o.n_runs = P->n_docs; o.payload_units = PU; o.pay_base = nullptr;
-    o.rel = nullptr; o.n_rel = 0; o.drec = nullptr; o.dcount = nullptr; o.dcap = 0;
-    o.dtext = nullptr; o.dtcap = 0; o.resume = nullptr; o.start = nullptr;
-    c->n_runs = P->n_docs;
-    c->batch_reg = false;                     // generated streams hold no register ops
-    c->batch_wide = mt_dev_wide(c);
     c->gen_off.assign(off.begin(), off.end());
-    c->run_off = c->gen_off; c->batch_gen++;
+    mt_install_batch(c, mt_dev_ops(c, P->n_docs, PU, false), off.data(), false, mt_dev_wide(c), false);   // (armed below)
     if (!P->continue_docs) {
         rc = MT_FN(docs_open)(c, 0, P->n_docs);
         if (rc) return rc;
@@ -1685,29 +1620,18 @@ int MT_FN(generated_copy_dev)(mt_ctx* c, uint32_t first, uint32_t n, mt_op_rec* 
 int MT_FN(upload_batch_dev)(mt_ctx* c, uint32_t n_runs, const uint32_t* doc_ids, const uint32_t* op_offsets,
                             const mt_op_rec* rec, const uint16_t* payload, uint64_t payload_units) {
     if (!c || !op_offsets || (n_runs && !doc_ids)) return MT_E_INVALID;
-    for (uint32_t r = 0; r < n_runs; r++) {
-        if (doc_ids[r] >= c->S.maxDocs) { c->err = "doc id out of range"; return MT_E_INVALID; }
-        if (op_offsets[r] > op_offsets[r + 1]) { c->err = "op_offsets not monotone"; return MT_E_INVALID; }
-    }
+    int rc;
+    if ((rc = mt_check_runs(c, n_runs, doc_ids, op_offsets))) return rc;
     const uint64_t N = op_offsets[n_runs];
     if (N && (!rec || !payload)) return MT_E_INVALID;
-    int rc;
-#define UP(buf, bytes) if ((rc = mtb_ensure(c, c->buf, (bytes)))) return rc;
+#define UP(buf, bytes) if ((rc = mtb_ensure(c, c->buf, (bytes)))) return mt_drop_batch(c, rc);
     UP(b_doc, 4ull * n_runs + 4) UP(b_off, 4ull * (n_runs + 1)) UP(b_rec, sizeof(MtOpRec) * N + 32) UP(b_pay, 2 * payload_units + 2)
 #undef UP
     mtb_h2d(c, c->b_doc.p, doc_ids, 4ull * n_runs);
     mtb_h2d(c, c->b_off.p, op_offsets, 4ull * (n_runs + 1));
     if (N) mtb_d2d(c, c->b_rec.p, rec, sizeof(MtOpRec) * N);
     if (payload_units) mtb_d2d(c, c->b_pay.p, payload, 2 * payload_units);
-    MtOps& o = c->ops;
-    o.doc_ids = (const uint32_t*)c->b_doc.p; o.op_off = (const uint32_t*)c->b_off.p; o.rec = (MtOpRec*)c->b_rec.p;
-    o.payload = (uint16_t*)c->b_pay.p; o.n_runs = n_runs; o.payload_units = payload_units; o.pay_base = nullptr;
-    o.rel = nullptr; o.n_rel = 0;
-    c->n_runs = n_runs;
-    c->run_off.assign(op_offsets, op_offsets + n_runs + 1); c->batch_gen++;
-    c->batch_reg = false;                     // device-built streams (shard.py) hold no register ops
-    c->batch_wide = mt_dev_wide(c);
-    c->gen.enabled = 0;
+    mt_install_batch(c, mt_dev_ops(c, n_runs, payload_units, false), op_offsets, false, mt_dev_wide(c), false);
     return mtb_sync(c);
 }
 // Document exchange rows (mt_shard.h): the sender packs generated runs at their plan
@@ -1734,10 +1658,8 @@ int MT_FN(upload_rows_dev)(mt_ctx* c, uint32_t n_runs, const uint32_t* doc_ids, 
                            const void* rows_dev, uint32_t payload_stride, const uint64_t* expect, uint32_t* bad_runs) {
     if (!c || !op_offsets || (n_runs && (!doc_ids || !expect)) || payload_stride == 0 || payload_stride % 4)
         return MT_E_INVALID;
-    for (uint32_t r = 0; r < n_runs; r++) {
-        if (doc_ids[r] >= c->S.maxDocs) { c->err = "doc id out of range"; return MT_E_INVALID; }
-        if (op_offsets[r] > op_offsets[r + 1]) { c->err = "op_offsets not monotone"; return MT_E_INVALID; }
-    }
+    int rc;
+    if ((rc = mt_check_runs(c, n_runs, doc_ids, op_offsets))) return rc;
     const uint64_t N = op_offsets[n_runs], L = payload_stride;
     if (N && !rows_dev) return MT_E_INVALID;
     // payload_off is relative to the run's base (op_off[run] * L, 64-bit), so only a run's own
@@ -1746,8 +1668,7 @@ int MT_FN(upload_rows_dev)(mt_ctx* c, uint32_t n_runs, const uint32_t* doc_ids, 
         if ((uint64_t)(op_offsets[r + 1] - op_offsets[r]) * L >= 0xFFFFFFFFull) {
             c->err = "one document's payload slots exceed 2^32 units"; return MT_E_INVALID;
         }
-    int rc;
-#define UP(buf, bytes) if ((rc = mtb_ensure(c, c->buf, (bytes)))) return rc;
+#define UP(buf, bytes) if ((rc = mtb_ensure(c, c->buf, (bytes)))) return mt_drop_batch(c, rc);
     UP(b_doc, 4ull * n_runs + 4) UP(b_off, 4ull * (n_runs + 1)) UP(b_rec, sizeof(MtOpRec) * N + 32) UP(b_pay, 2 * N * L + 2)
     UP(b_tmp1, 8ull * n_runs + 8) UP(b_pbase, 8ull * n_runs + 8)
 #undef UP
@@ -1758,16 +1679,7 @@ int MT_FN(upload_rows_dev)(mt_ctx* c, uint32_t n_runs, const uint32_t* doc_ids, 
         for (uint32_t r = 0; r < n_runs; r++) pbase[r] = (unsigned long long)op_offsets[r] * L;
         if (n_runs) mtb_h2d(c, c->b_pbase.p, pbase.data(), 8ull * n_runs);
     }
-    MtOps& o = c->ops;
-    o.doc_ids = (const uint32_t*)c->b_doc.p; o.op_off = (const uint32_t*)c->b_off.p; o.rec = (MtOpRec*)c->b_rec.p;
-    o.payload = (uint16_t*)c->b_pay.p; o.n_runs = n_runs; o.payload_units = N * L;
-    o.pay_base = (const unsigned long long*)c->b_pbase.p;
-    o.rel = nullptr; o.n_rel = 0;
-    c->n_runs = n_runs;
-    c->run_off.assign(op_offsets, op_offsets + n_runs + 1); c->batch_gen++;
-    c->batch_reg = false;                     // exchanged generated streams hold no register ops
-    c->batch_wide = mt_dev_wide(c);
-    c->gen.enabled = 0;
+    mt_install_batch(c, mt_dev_ops(c, n_runs, N * L, true), op_offsets, false, mt_dev_wide(c), false);
     if (n_runs && (rc = mtb_launch_rows(c, false, 0, n_runs, (uint32_t)L, nullptr, (uint64_t*)rows_dev,
                                         (uint64_t*)c->b_tmp1.p))) return rc;
     if ((rc = mtb_sync(c))) return rc;

@@ -6,6 +6,7 @@
 #include "mt_replay.h"
 #include "mt_snapshot.h"
 #include "mt_pack.h"
+#include "mt_pools.h"
 #include "mt_query.h"
 
 struct mt_ctx {
@@ -16,9 +17,8 @@ struct mt_ctx {
     std::vector<MtDocLayout> layout_h;                                     // host copy of S.layout
     uint64_t pool_bytes = 0;
     MtDocLayout tot{};                                                     // pool element totals
-    // mt_checkpoint shadows (device)
-    void *ck_rows = nullptr, *ck_blk = nullptr, *ck_heap = nullptr, *ck_win = nullptr, *ck_text = nullptr,
-         *ck_pset = nullptr, *ck_hdr = nullptr, *ck_hold = nullptr, *ck_ovx = nullptr, *ck_mid = nullptr, *ck_reg = nullptr, *ck_regr = nullptr;
+    // mt_checkpoint shadows (device) and their allocated bytes, indexed as MT_POOLS is
+    void* ck[MT_NPOOLS] = {nullptr}; size_t ck_bytes[MT_NPOOLS] = {0};
     bool ck_valid = false;
     // Growth (mt_docs_resize / mt_set_autogrow).  The per-document pools are allocated for
     // `cap` elements, of which `tot` are handed out: a relocated document's new slices go at
@@ -29,7 +29,6 @@ struct mt_ctx {
     MtDocLayout cap{};
     std::vector<MtDocLayout> ck_layout;
     MtDocLayout ck_tot{}, ck_dead{};
-    size_t ck_bytes[12] = {0};                     // allocated bytes of each shadow (mt_ck_parts order)
     MtDocLayout dead{};                            // vacated elements per pool
     bool autogrow = false; uint64_t grow_budget = 0;
     uint64_t grow_reloc = 0, grow_realloc = 0, grow_moved = 0;

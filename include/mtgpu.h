@@ -436,7 +436,14 @@ int  mt_set_props(mt_ctx* ctx, const mt_prop_table* props);
 int  mt_apply_batch(mt_ctx* ctx, const mt_op_batch* batch);
 
 /* Upload a batch once and keep it resident; mt_replay_resident replays it on the
- * documents it names without any host->device traffic (the bench's timed path). */
+ * documents it names without any host->device traffic (the bench's timed path).
+ * A failed upload: mt_upload_batch validates the whole batch before it touches anything, so
+ * MT_E_INVALID leaves the batch that was resident as it was.  mt_upload_batch_parts validates
+ * the run lists first (a failure there keeps the old batch too) but the ops only while it packs
+ * them, after the resident region may have been replaced by a larger one: an op it refuses
+ * (MT_E_INVALID), and any allocation failure of either call (MT_E_OOM), leaves no batch
+ * resident, generated streams included; mt_replay_resident returns MT_E_INVALID until the
+ * next successful upload. */
 int  mt_upload_batch(mt_ctx* ctx, const mt_op_batch* batch);
 int  mt_replay_resident(mt_ctx* ctx);
 /* Several batches applied as one (runs in part order): a host that packs on several threads

@@ -34,6 +34,11 @@ def test_gpu_explicit_resize_mid_stream(armed):
     tg.check_explicit_resize(gpu_engine, armed)
 
 
+def test_gpu_pool_accounting():
+    from test_pool_accounting import check_pool_accounting
+    check_pool_accounting(gpu_engine)
+
+
 def test_gpu_capture_with_growth_matches_oracle():
     tg.check_capture_with_growth(gpu_engine)
 
