@@ -25,6 +25,7 @@ MT_OPF_CONSENSUS, MT_OPF_INCR_STRMIN = 2, 8          # on combining annotates (i
 MT_OP_CUT, MT_OP_COPY, MT_OP_PASTE = 5, 6, 7      # register ops (include/mtgpu.h)
 MT_OPF_REL1, MT_OPF_REL2, MT_OPF_MARKER_ID = 0x20, 0x40, 0x80
 MARKER_ID_KEY = "markerId"            # reservedMarkerIdKey, MT/mergeTree.ts:591
+TILE_LABELS_KEY = "referenceTileLabels"   # reservedTileLabelsKey, MT/mergeTree.ts:589
 # property values other than interned ids (include/mtgpu.h MT_VAL_*, MT_VK_*)
 MT_VAL_NULL, MT_VAL_NAN, MT_VAL_UNSUP, MT_VAL_CFRESH, MT_VAL_UNDEF, MT_VAL_THROW, MT_VAL_CONS_BASE = -1, -2, -3, -4, -5, -6, -16
 INCR_CHAIN_MAX = 64        # incr results of a held string precomputed per value (PropTable.to_c)
@@ -202,6 +203,27 @@ class PropTable:
             self._c = None
         return i
 
+    def tile_match(self, labels) -> np.ndarray:
+        """mt_tile_labels.match for `labels` (strings): a uint8 array [len(labels), n_values], 1
+        where iterating the value as the reference's refHasTileLabel does (a JS for..of with ===,
+        MT/mergeTree.ts:594-610) yields the label: an array matches by element, a string by code
+        point; other values, and elements that are not strings, never equal a string label."""
+        import json as _json
+        labels = list(labels)
+        m = np.zeros((len(labels), len(self.values_json)), np.uint8)
+        for v, txt in enumerate(self.values_json):
+            val = _json.loads(txt)
+            if isinstance(val, list):
+                items = {x for x in val if isinstance(x, str)}
+            elif isinstance(val, str):
+                items = set(val)            # json.loads joins surrogate pairs: code points
+            else:
+                continue
+            for i, lab in enumerate(labels):
+                if lab in items:
+                    m[i, v] = 1
+        return m
+
     def _incr_table(self):
         """(value_incr, incr_object) for mt_prop_table: what incr yields from each value held
         (properties.ts:33-34, `v += undefined`): the id of String(v) + "undefined" for a string,
@@ -360,6 +382,10 @@ class BatchBuilder:
         self.doc_ids: list[int] = []
         self.offsets: list[int] = [0]
         self.rel: list[tuple] = []
+        # documents an annotate naming referenceTileLabels was packed for: the reference's block
+        # tile caches go stale there (annotateRange runs no blockUpdate, mergeTree.ts:2584-2624),
+        # so tile search on them is not reproduced (MergeTreeClient.findTile raises)
+        self.tile_annotated: set[int] = set()
 
     def begin_doc(self, doc_id: int):
         if len(self.doc_ids) and self.offsets[-1] == len(self.cols["type"]) and len(self.doc_ids) == len(self.offsets) - 1:
@@ -460,6 +486,8 @@ class BatchBuilder:
             if t == MT_OP_ANNOTATE:
                 # segmentPropertiesManager.ts:55-56: rewrite = op && op.name === "rewrite", any other
                 # truthy combiningOp combines (properties.ts:24-62)
+                if isinstance(op.get("props"), dict) and TILE_LABELS_KEY in op["props"] and self.doc_ids:
+                    self.tile_annotated.add(self.doc_ids[-1])
                 cop = op.get("combiningOp")
                 combine = jsjson.js_truthy(cop) and not (isinstance(cop, dict) and cop.get("name") == "rewrite")
                 if jsjson.js_truthy(cop) and not combine:

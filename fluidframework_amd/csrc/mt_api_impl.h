@@ -1159,8 +1159,10 @@ int MT_FN(get_length)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t
 // Position queries (mt_query.h): sorted by document (stable), one wave per document's group,
 // answers back in query order; the found segments' text gathered on the device, their JSON
 // written here from the text and the property-map chunks the kernel copied.
+// kind: MT_QK_LOCAL for position queries (a caller's ref_seq < 0 is the local view whatever its
+// value), else the tile-search kind every query of the call carries in `ref` (mt_query.h).
 static int mt_run_queries(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t* pos, const int32_t* ref,
-                          const int32_t* cli, std::vector<MtQueryOut>& res) {
+                          const int32_t* cli, std::vector<MtQueryOut>& res, int kind = MT_QK_LOCAL) {
     res.assign(n, MtQueryOut{});
     if (n == 0) return MT_OK;
     for (uint32_t i = 0; i < n; i++) if (docs[i] >= c->S.maxDocs) { c->err = "query document out of range"; return MT_E_INVALID; }
@@ -1171,7 +1173,8 @@ static int mt_run_queries(mt_ctx* c, uint32_t n, const uint32_t* docs, const int
     std::vector<uint32_t> grp;
     for (uint32_t k = 0; k < n; k++) {
         const uint32_t i = ord[k];
-        q[k].doc = docs[i]; q[k].pos = pos[i]; q[k].ref = ref ? ref[i] : -1; q[k].client = cli ? cli[i] : -1;
+        q[k].doc = docs[i]; q[k].pos = pos[i]; q[k].client = cli ? cli[i] : -1;
+        q[k].ref = kind != MT_QK_LOCAL ? kind : ((ref && ref[i] >= 0) ? ref[i] : MT_QK_LOCAL);
         if (k == 0 || docs[i] != docs[ord[k - 1]]) grp.push_back(k);
     }
     grp.push_back(n);
@@ -1191,14 +1194,12 @@ static int mt_run_queries(mt_ctx* c, uint32_t n, const uint32_t* docs, const int
     return MT_OK;
 }
 
-int MT_FN(get_containing_segment)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t* pos, const int32_t* ref,
-                                  const int32_t* cli, mt_seg_info* out, const char** json_arena, const uint64_t** json_off) {
-    if (!c || (n && (!docs || !pos))) return MT_E_INVALID;
-    std::vector<MtQueryOut> res;
-    int rc = mt_run_queries(c, n, docs, pos, ref, cli, res);
-    if (rc) return rc;
-    if (out) for (uint32_t i = 0; i < n; i++) out[i] = res[i].info;
+// The found segments' JSON (toJSONObject) into the library-owned arena: their text gathered on
+// the device, the property maps from the chunks the kernel copied.
+static int mt_seg_json(mt_ctx* c, uint32_t n, const std::vector<MtQueryOut>& res, const char** json_arena,
+                       const uint64_t** json_off) {
     if (!json_arena) return MT_OK;
+    int rc;
     // text of the found text segments, gathered on the device into one arena
     std::vector<unsigned long long> at, off(1, 0);
     std::vector<uint32_t> len, which;
@@ -1240,6 +1241,80 @@ int MT_FN(get_containing_segment)(mt_ctx* c, uint32_t n, const uint32_t* docs, c
     }
     *json_arena = c->seg_json_arena.data();
     if (json_off) *json_off = c->seg_json_off.data();
+    return MT_OK;
+}
+
+int MT_FN(get_containing_segment)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t* pos, const int32_t* ref,
+                                  const int32_t* cli, mt_seg_info* out, const char** json_arena, const uint64_t** json_off) {
+    if (!c || (n && (!docs || !pos))) return MT_E_INVALID;
+    std::vector<MtQueryOut> res;
+    int rc = mt_run_queries(c, n, docs, pos, ref, cli, res);
+    if (rc) return rc;
+    if (out) for (uint32_t i = 0; i < n; i++) out[i] = res[i].info;
+    return mt_seg_json(c, n, res, json_arena, json_off);
+}
+
+// Tile search (mt_query.h): the labels' match arrays go to the device and into MtState, where
+// the query kernel's tile kinds read them.
+static int mt_tile_setup(mt_ctx* c, const mt_tile_labels* T, uint32_t n, const uint32_t* label) {
+    if (!T || (T->n_labels && T->n_values && !T->match)) { c->err = "tile labels missing"; return MT_E_INVALID; }
+    if (T->n_values != c->names.value_json.size()) { c->err = "tile labels: n_values differs from the uploaded prop table"; return MT_E_INVALID; }
+    if (T->n_labels >= (uint32_t)MT_QT_PRECEDING) { c->err = "too many tile labels"; return MT_E_INVALID; }
+    for (uint32_t i = 0; i < n; i++) if (label[i] >= T->n_labels) { c->err = "tile label out of range"; return MT_E_INVALID; }
+    const size_t bytes = (size_t)T->n_labels * T->n_values;
+    int rc;
+    if ((rc = mtb_ensure(c, c->b_tmatch, bytes + 1))) return rc;
+    if ((rc = mtb_sync(c))) return rc;
+    if (bytes) mtb_h2d(c, c->b_tmatch.p, T->match, bytes);
+    c->S.t_match = (const uint8_t*)c->b_tmatch.p; c->S.t_key = T->key; c->S.t_nvalues = T->n_values;
+    c->S.t_out = nullptr; c->S.t_cap = 0;
+    return MT_OK;
+}
+
+int MT_FN(find_tile)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t* pos, const uint8_t* flags,
+                     const uint32_t* label, const mt_tile_labels* labels, mt_seg_info* out, const char** json_arena,
+                     const uint64_t** json_off) {
+    if (!c || (n && (!docs || !pos || !label))) return MT_E_INVALID;
+    for (uint32_t i = 0; i < n; i++)
+        if (pos[i] < 0 && pos[i] != MT_POS_UNDEFINED) { c->err = "findTile: negative start position"; return MT_E_INVALID; }
+    int rc = mt_tile_setup(c, labels, n, label);
+    if (rc) return rc;
+    std::vector<int32_t> arg(n);
+    for (uint32_t i = 0; i < n; i++) arg[i] = (int32_t)label[i] | ((flags && (flags[i] & MT_TILE_PRECEDING)) ? MT_QT_PRECEDING : 0);
+    std::vector<MtQueryOut> res;
+    if ((rc = mt_run_queries(c, n, docs, pos, nullptr, arg.data(), res, MT_QK_TILE))) return rc;
+    if (out) for (uint32_t i = 0; i < n; i++) out[i] = res[i].info;
+    return mt_seg_json(c, n, res, json_arena, json_off);
+}
+
+int MT_FN(tile_index)(mt_ctx* c, uint32_t n, const uint32_t* docs, const uint32_t* label, const mt_tile_labels* labels,
+                      const mt_tile_rec** recs, const uint64_t** rec_off) {
+    if (!c || !recs || !rec_off || (n && (!docs || !label))) return MT_E_INVALID;
+    int rc = mt_tile_setup(c, labels, n, label);
+    if (rc) return rc;
+    // two passes over the same scan, as mt_pack_size / mt_pack_doc: count, then fill at the
+    // offsets the counts give
+    std::vector<int32_t> at(n, 0), arg(label, label + n);
+    std::vector<MtQueryOut> res;
+    if ((rc = mt_run_queries(c, n, docs, at.data(), nullptr, arg.data(), res, MT_QK_TILE_COUNT))) return rc;
+    c->tile_off.assign((size_t)n + 1, 0);
+    for (uint32_t i = 0; i < n; i++) c->tile_off[i + 1] = c->tile_off[i] + (uint64_t)(uint32_t)res[i].info.found;
+    const uint64_t total = c->tile_off[n];
+    if (total > 0xFFFFFFFFull) { c->err = "tile index: more than 2^32 records"; return MT_E_INVALID; }
+    c->tile_recs.assign((size_t)total, mt_tile_rec{});
+    if (total) {
+        if ((rc = mtb_ensure(c, c->b_tout, sizeof(mt_tile_rec) * total))) return rc;
+        c->S.t_out = (mt_tile_rec*)c->b_tout.p; c->S.t_cap = total;
+        for (uint32_t i = 0; i < n; i++) at[i] = (int32_t)(uint32_t)c->tile_off[i];
+        rc = mt_run_queries(c, n, docs, at.data(), nullptr, arg.data(), res, MT_QK_TILE_FILL);
+        c->S.t_out = nullptr; c->S.t_cap = 0;
+        if (rc) return rc;
+        for (uint32_t i = 0; i < n; i++)
+            if ((uint64_t)(uint32_t)res[i].info.found != c->tile_off[i + 1] - c->tile_off[i]) { c->err = "tile index: the passes disagree"; return MT_E_INVALID; }
+        mtb_d2h(c, c->tile_recs.data(), c->b_tout.p, sizeof(mt_tile_rec) * total);
+    }
+    *recs = c->tile_recs.data();
+    *rec_off = c->tile_off.data();
     return MT_OK;
 }
 

@@ -307,6 +307,11 @@ struct MtState {                              // device pools, doc-major
     // and MT_VINFO_SEQM1; element -1: incr of a fresh consensus object (null: combine sets
     // unsupported); mt_set_props
     const int32_t* p_vinfo;
+    // tile search (mt_query.h; set per call by mt_find_tile / mt_tile_index): the labels' match
+    // arrays ([label * t_nvalues + value id]), the key id of "referenceTileLabels", and the
+    // index's record array (t_cap records)
+    const uint8_t* t_match; uint32_t t_key, t_nvalues;
+    mt_tile_rec* t_out; unsigned long long t_cap;
 };
 #define MT_VINFO_ID    0x3FFFFFFF
 #define MT_VINFO_NONE  0x3FFFFFFF

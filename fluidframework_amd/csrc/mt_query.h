@@ -2,13 +2,25 @@
 //   MergeTree.getContainingSegment        MT/mergeTree.ts:1616-1627 (searchBlock :1786-1815)
 //   MergeTree.resolveRemoteClientPosition MT/mergeTree.ts:2125-2145
 //   MergeTree.getPosition                 MT/mergeTree.ts:1578-1596 (the local view)
+// and tile search (mt_find_tile, mt_tile_index) over a document-order scan of the rows:
+//   MergeTree.findTile                    MT/mergeTree.ts:1752-1778 (search :1780-1820,
+//                                         backwardSearch :1822-1866; the rule: include/mtgpu.h)
 // Batched: the host groups the queries by document, one wave takes a document's queries
 // in order (the perspective's U set is reused while consecutive queries share it).  A
-// query reads the document and writes only the wave's U scratch of that document.
+// query reads the document and writes only the wave's U scratch of that document; a tile
+// query writes nothing of the document at all (its stack is the wave's LDS scratch).
 #pragma once
 #include "mt_core.h"
 
-struct __attribute__((aligned(16))) MtQuery { uint32_t doc; int32_t pos, ref, client; };   // ref < 0: local view
+// ref < 0 selects the query's kind: the local view, or a tile search (client: the label's
+// index, with MT_QT_PRECEDING for findTile's `preceding`; pos: startPos, or the first record
+// of the document for the index's fill pass)
+#define MT_QK_LOCAL (-1)
+#define MT_QK_TILE (-2)
+#define MT_QK_TILE_COUNT (-3)
+#define MT_QK_TILE_FILL (-4)
+#define MT_QT_PRECEDING 0x40000000
+struct __attribute__((aligned(16))) MtQuery { uint32_t doc; int32_t pos, ref, client; };   // ref < 0: local view / kind
 // One answer: the ABI record, where the found row's text sits in the text pool, and the
 // chunks of its property map (the host writes the segment's JSON from them).
 struct __attribute__((aligned(16))) MtQueryOut {
@@ -18,11 +30,341 @@ struct __attribute__((aligned(16))) MtQueryOut {
     MtPSet ps[MT_PKEYS / MT_PSK];
 };
 static_assert(sizeof(mt_seg_info) == 64, "mt_seg_info is 16 dwords");
+static_assert(sizeof(mt_tile_rec) == 32, "mt_tile_rec is 8 dwords");
+
+/* ------------------------------------------------------- document-order scan -- */
+// The rows of a document in document order, a unit at a time.  A unit is the up-to-64 rows
+// under one block of height 1 (lane l: row l & 7 of leaf block l >> 3), or the root's up-to-8
+// rows when the tree has height 0.  The cursor's stack (block, child index, observer start
+// per level above the unit) lives in the wave's scratch (MtScratch::pathB / pathJ / pathOff).
+// Control flow is wave-uniform; a unit's rows are lane data.
+struct MtTileCursor {
+    int U;           // the unit's block (-1: past either end)
+    int lvl;         // stack levels above the unit
+    int base;        // observer start of the unit
+};
+// One unit's rows: ids (-1: no row in that lane), the quads' fields, the visible lengths'
+// exclusive scans (all rows / text rows only) and the candidate masks.
+struct MtTileUnit {
+    LaneArr<int> row, len, seq, rseq, toff, props, pre, tpre;
+    LaneArr<uint32_t> meta;
+    uint64_t present;    // lanes holding a row
+    uint64_t cand;       // visible Tile markers
+    uint64_t candAny;    // Tile markers, removed ones included
+    int vis, tvis;       // the unit's visible length, and that of its text rows
+    int height;          // the unit block's height (0: the root alone)
+};
+enum { MT_TD_POS = 0, MT_TD_FIRST_VIS, MT_TD_LAST_VIS, MT_TD_FIRST, MT_TD_LAST };
+
+template <class Eng> MT_HD bool mt_tile_blk_ok(const Eng& e, int b) { return b >= 0 && b < e.blkTop; }
+
+// Down from block B (observer start `base`) to a unit: at each level the child holding
+// observer position P (MT_TD_POS; P < the block's length), the first / last child of non-zero
+// observer length, or the first / last child.  False: no such child (or a broken tree).
+template <class Eng>
+MT_HD bool mt_tile_down(Eng& e, MtTileCursor& c, int B, int base, int P, int mode) {
+    for (;;) {
+        if (!mt_tile_blk_ok(e, B)) { c.U = -1; return false; }
+        if (uni(e.bk(B).height) <= 1) { c.U = B; c.base = base; return true; }
+        if (c.lvl >= MT_MAXH + 1) { c.U = -1; return false; }
+        BlkH h;
+        const auto ch = e.blkLoad(B, h);
+        const int n = h.n < 0 ? 0 : (h.n > MT_MAXN ? MT_MAXN : h.n);
+        const int top = e.blkTop;
+        const auto lens = wave_map(n, [&](int j) MT_LAM {
+            const int b = own(ch, j);
+            const bool ok = (b >= 0) & (b < top);
+            return ok ? e.bk(ok ? b : 0).len : 0;
+        });
+        const auto pre = wave_excl_scan8(lens);
+        int j;
+        if (mode == MT_TD_POS) {
+            const int p = P - base;
+            j = wave_first(wave_map(n, [&](int k) MT_LAM { return p - own(pre, k) < own(lens, k); }));
+        } else if (mode == MT_TD_FIRST_VIS || mode == MT_TD_LAST_VIS) {
+            const uint64_t m = wave_ballot(wave_map(n, [&](int k) MT_LAM { return own(lens, k) > 0; }));
+            j = !m ? -1 : (mode == MT_TD_FIRST_VIS ? __builtin_ctzll(m) : 63 - __builtin_clzll(m));
+        } else j = mode == MT_TD_FIRST ? 0 : n - 1;
+        if (j < 0 || j >= n) { c.U = -1; return false; }
+        e.sc->pathB[c.lvl] = B; e.sc->pathJ[c.lvl] = j; e.sc->pathOff[c.lvl] = base;
+        wave_sync();
+        c.lvl++;
+        base += wave_at(pre, j);
+        B = wave_at(ch, j);
+    }
+}
+// The next unit to the right (dir > 0) or left (dir < 0) of the cursor's; all: every unit,
+// else only units of non-zero observer length (a subtree of length 0 holds no visible row).
+template <class Eng>
+MT_HD bool mt_tile_next(Eng& e, MtTileCursor& c, int dir, bool all) {
+    while (c.lvl > 0) {
+        const int l = c.lvl - 1;
+        const int B = uni(e.sc->pathB[l]), j = uni(e.sc->pathJ[l]), base = uni(e.sc->pathOff[l]);
+        BlkH h;
+        const auto ch = e.blkLoad(B, h);
+        const int n = h.n < 0 ? 0 : (h.n > MT_MAXN ? MT_MAXN : h.n);
+        const int top = e.blkTop;
+        const auto lens = wave_map(n, [&](int k) MT_LAM {
+            const int b = own(ch, k);
+            const bool ok = (b >= 0) & (b < top);
+            return ok ? e.bk(ok ? b : 0).len : 0;
+        });
+        const auto pre = wave_excl_scan8(lens);
+        const uint64_t m = wave_ballot(wave_map(n, [&](int k) MT_LAM {
+            return (((dir > 0) ? (k > j) : (k < j)) & ((own(lens, k) > 0) | all)) != 0;
+        }));
+        if (m) {
+            const int k = dir > 0 ? __builtin_ctzll(m) : 63 - __builtin_clzll(m);
+            e.sc->pathJ[l] = k;
+            wave_sync();
+            const int mode = dir > 0 ? (all ? MT_TD_FIRST : MT_TD_FIRST_VIS) : (all ? MT_TD_LAST : MT_TD_LAST_VIS);
+            return mt_tile_down(e, c, wave_at(ch, k), base + wave_at(pre, k), 0, mode);
+        }
+        c.lvl--;
+    }
+    c.U = -1;
+    return false;
+}
+// Loads the cursor's unit: each lane its leaf block's child id and count, then the row's
+// first two quads (len seq rseq meta | toff props parent tcap), as scourLeaves does.
+template <class Eng>
+MT_HD void mt_tile_unit(Eng& e, const MtTileCursor& c, MtTileUnit& u) {
+    BlkH h;
+    const auto ch = e.blkLoad(c.U, h);
+    u.height = h.height;
+    const int U = c.U, hn = h.n < 0 ? 0 : (h.n > MT_MAXN ? MT_MAXN : h.n);
+    const bool leafRoot = h.height == 0;
+    const int nb = leafRoot ? 1 : hn;
+    const auto blks = wave_map(8, [&](int j) MT_LAM { return leafRoot ? (j == 0 ? U : -1) : own(ch, j); });
+    const int span = 8 * nb;
+    const auto bsel = wave_gather8(blks);
+    const int btop = e.blkTop, rtop = e.rowTop;
+    u.row = wave_map(span, [&](int t) MT_LAM {
+        const int b = own(bsel, t);
+        const bool ok = (b >= 0) & (b < btop);
+        const int bb = ok ? b : 0;
+        const int g = e.bk(bb).c[t & 7];
+        return (ok & ((t & 7) < e.bk(bb).n) & (g >= 0) & (g < rtop)) ? g : -1;
+    });
+    const auto q0 = wave_map(span, [&](int t) MT_LAM {
+        const int g = own(u.row, t);
+        return g >= 0 ? ((const MtQ16a*)&e.row(g))[0] : MtQ16a{0u, 0u, 0u, 0u};
+    });
+    const auto q1 = wave_map(span, [&](int t) MT_LAM {
+        const int g = own(u.row, t);
+        return g >= 0 ? ((const MtQ16a*)&e.row(g))[1] : MtQ16a{0u, 0u, 0u, 0u};
+    });
+    u.len = wave_map(span, [&](int t) MT_LAM { return (int)own(q0, t).x; });
+    u.seq = wave_map(span, [&](int t) MT_LAM { return (int)own(q0, t).y; });
+    u.rseq = wave_map(span, [&](int t) MT_LAM { return (int)own(q0, t).z; });
+    u.meta = wave_map(span, [&](int t) MT_LAM { return own(q0, t).w; });
+    u.toff = wave_map(span, [&](int t) MT_LAM { return (int)own(q1, t).x; });
+    u.props = wave_map(span, [&](int t) MT_LAM { return (int)own(q1, t).y; });
+    u.present = wave_ballot(wave_map(span, [&](int t) MT_LAM { return own(u.row, t) >= 0; }));
+    // the candidate test, branch-free per lane: marker, refType & Tile, not removed
+    u.candAny = wave_ballot(wave_map(span, [&](int t) MT_LAM {
+        return ((own(u.row, t) >= 0) & ((own(u.meta, t) & MT_M_MARKER) != 0) & ((own(u.toff, t) & 1) != 0)) != 0;
+    }));
+    u.cand = u.candAny & wave_ballot(wave_map(span, [&](int t) MT_LAM { return (own(u.meta, t) & MT_M_REMOVED) == 0; }));
+    const auto vl = wave_map(span, [&](int t) MT_LAM {
+        return ((own(u.row, t) >= 0) & ((own(u.meta, t) & MT_M_REMOVED) == 0)) ? own(u.len, t) : 0;
+    });
+    const auto tl = wave_map(span, [&](int t) MT_LAM { return (own(u.meta, t) & MT_M_MARKER) ? 0 : own(vl, t); });
+    u.pre = wave_excl_scan(vl);
+    u.tpre = wave_excl_scan(tl);
+    u.vis = wave_sum(vl);
+    u.tvis = wave_sum(tl);
+}
+
+// Does property map `ps` yield label `lab`?  The wave reads the map one key per lane, in
+// rounds of 64, looks for the key id of "referenceTileLabels" and tests that key's value id
+// against the label's match array.  Maps are immutable and shared between segments: the last
+// map tested and its result are remembered (wave-uniform).
+struct MtTileMemo { int lab, ps; bool res; };
+template <class Eng>
+MT_HD bool mt_tile_map_has(Eng& e, const MtState& S, int ps, int lab, MtTileMemo& memo) {
+    if (ps < 0 || ps >= e.psetTop) return false;
+    if (memo.ps == ps && memo.lab == lab) return memo.res;
+    int n = uni(e.pset[ps].n);
+    const int room = (e.psetTop - ps) * MT_PSK;
+    n = n < 0 ? 0 : (n > MT_PKEYS ? MT_PKEYS : n);
+    n = n > room ? room : n;
+    const int key = (int)S.t_key;
+    const uint32_t nv = S.t_nvalues;
+    const uint8_t* mrow = S.t_match + (size_t)lab * nv;
+    bool res = false;
+    for (int base = 0; base < n && !res; base += MT_WAVE) {
+        const int m = (n - base) < MT_WAVE ? (n - base) : MT_WAVE;
+        res = wave_ballot(wave_map(m, [&](int k) MT_LAM {
+            const int v = e.pval(ps, base + k);
+            const bool q = (e.pkey(ps, base + k) == key) & (v >= 0) & ((uint32_t)v < nv);
+            return (q & (mrow[q ? v : 0] != 0)) != 0;
+        })) != 0;
+    }
+    memo.ps = ps; memo.lab = lab; memo.res = res;
+    return res;
+}
+
+// One answer record (the 16 dwords of mt_seg_info, the row's text, its map's chunks): row s
+// found at `off` into it with observer start op; s < 0: not found, `resolved` as given.
+template <class Eng>
+MT_HD void mt_query_emit(Eng& e, const MtState& S, MtQueryOut& o, int s, int off, int op, int depth,
+                         unsigned long long path, int resolved) {
+    int f[16];
+    for (int k = 0; k < 16; k++) f[k] = 0;
+    unsigned long long tat = 0;
+    int nch = 0, ps = -1;
+    if (s >= 0) {
+        const uint32_t mt = uni(e.row(s).meta);
+        const bool removed = (mt & MT_M_REMOVED) != 0, marker = (mt & MT_M_MARKER) != 0;
+        const int cl = (int)(mt & MT_M_CLIENT);
+        ps = uni(e.row(s).props);
+        f[0] = 1; f[1] = off; f[2] = op; f[3] = uni(e.row(s).len); f[4] = uni(e.row(s).seq);
+        f[5] = cl == MT_NONCOLLAB ? -1 : cl;
+        f[6] = removed ? uni(e.row(s).rseq) : (int)0x80000000;
+        f[7] = removed ? (int)uni(e.row(s).rcl) : -1;
+        f[8] = ps; f[9] = marker ? uni(e.row(s).toff) : -1;
+        f[10] = depth; f[11] = (int)(uint32_t)path; f[12] = (int)(uint32_t)(path >> 32);
+        f[13] = s; f[14] = op + off;
+        if (!marker) tat = (unsigned long long)(e.text - S.text) + (unsigned long long)uni(e.row(s).toff);
+        if (ps >= 0) { const int n = uni(e.pset[ps].n); nch = n > MT_PSK ? (n + MT_PSK - 1) / MT_PSK : 1; }
+    } else {
+        f[1] = -1; f[2] = -1; f[5] = -1; f[6] = (int)0x80000000; f[7] = -1; f[8] = -1; f[9] = -1; f[13] = -1;
+        f[14] = resolved;
+    }
+    const auto fv = wave_map(16, [&](int k) MT_LAM { return pick16(f, k); });
+    wave_for(16, [&](int k) MT_LAM { ((int*)&o.info)[k] = own(fv, k); });
+    wave_for(1, [&](int) MT_LAM { o.text_at = tat; o.pad = 0; });
+    // the property map's chunks, one dword per lane (28 dwords a chunk)
+    constexpr int W = (int)(sizeof(MtPSet) / 4);
+    for (int base = 0; base < nch * W; base += MT_WAVE) {
+        const int m = (nch * W - base) < MT_WAVE ? (nch * W - base) : MT_WAVE;
+        wave_for(m, [&](int k) MT_LAM { ((int*)o.ps)[base + k] = ((const int*)(e.pset + ps))[base + k]; });
+    }
+    wave_sync();
+}
+
+// The tree path of lane t of the cursor's unit, root first, 3 bits a level (as containing's).
+template <class Eng>
+MT_HD unsigned long long mt_tile_path(Eng& e, const MtTileCursor& c, const MtTileUnit& u, int t, int& depth) {
+    unsigned long long path = 0;
+    for (int l = 0; l < c.lvl; l++) path = (path << 3) | (unsigned long long)(uni(e.sc->pathJ[l]) & 7);
+    depth = c.lvl + 1;
+    if (u.height != 0) { path = (path << 3) | (unsigned long long)(t >> 3); depth++; }
+    return (path << 3) | (unsigned long long)(t & 7);
+}
+
+// findTile (the rule: include/mtgpu.h).  Returns the row (-1: undefined) with its observer
+// start, depth and path.
+template <class Eng>
+MT_HD int mt_find_tile_doc(Eng& e, const MtState& S, int pos, int lab, bool preceding, MtTileMemo& memo, int& op, int& depth,
+                           unsigned long long& path) {
+    if (!mt_tile_blk_ok(e, e.root)) return -1;
+    const int L = uni(e.bk(e.root).len);
+    const bool undef = pos == (int)0x80000000;
+    MtTileCursor c; c.U = -1; c.lvl = 0; c.base = 0;
+    MtTileUnit u;
+    if (!preceding && !undef && pos >= L) {
+        if (pos > L) return -1;
+        // the leaf is the document's last row (`pos >= segpos` holds for every row): the
+        // answer if it matches, removed or not (MT/mergeTree.ts:1841-1855, :993-1007)
+        if (!mt_tile_down(e, c, e.root, 0, 0, MT_TD_LAST)) return -1;
+        for (;;) {
+            mt_tile_unit(e, c, u);
+            if (u.present) break;
+            if (!mt_tile_next(e, c, -1, true)) return -1;
+        }
+        const int t = 63 - __builtin_clzll(u.present);
+        if (!((u.candAny >> t) & 1ull) || !mt_tile_map_has(e, S, wave_at(u.props, t), lab, memo)) return -1;
+        op = c.base + wave_at(u.pre, t);
+        path = mt_tile_path(e, c, u, t, depth);
+        return wave_at(u.row, t);
+    }
+    if (L <= 0) return -1;                          // no visible row
+    const int dir = preceding ? -1 : 1;
+    // the unit holding the start position; every comparison with an undefined pos is false
+    const int at = preceding ? ((undef || pos >= L) ? L - 1 : pos) : (undef ? 0 : pos);
+    const int lim = preceding ? ((undef || pos >= L) ? 0x7FFFFFFF : pos) : (undef ? 0 : pos);
+    if (!mt_tile_down(e, c, e.root, 0, at, MT_TD_POS)) return -1;
+    for (;;) {
+        mt_tile_unit(e, c, u);
+        const int ub = c.base;
+        uint64_t m = u.cand & wave_ballot(wave_map(MT_WAVE, [&](int t) MT_LAM {
+            const int st = ub + own(u.pre, t);
+            return dir < 0 ? st <= lim : st >= lim;
+        }));
+        while (m) {                                 // candidates nearest first
+            const int t = dir < 0 ? 63 - __builtin_clzll(m) : __builtin_ctzll(m);
+            m &= ~(1ull << t);
+            if (mt_tile_map_has(e, S, wave_at(u.props, t), lab, memo)) {
+                op = ub + wave_at(u.pre, t);
+                path = mt_tile_path(e, c, u, t, depth);
+                return wave_at(u.row, t);
+            }
+        }
+        if (!mt_tile_next(e, c, dir, false)) return -1;
+    }
+}
+
+// The tile index of one document: every visible matching tile in document order.  out null:
+// count only.  Returns the count; records go to out[0 .. count), as far as `room` reaches.
+template <class Eng>
+MT_HD int mt_tile_index_doc(Eng& e, const MtState& S, int lab, MtTileMemo& memo, mt_tile_rec* out, unsigned long long room) {
+    if (!mt_tile_blk_ok(e, e.root) || uni(e.bk(e.root).len) <= 0) return 0;
+    MtTileCursor c; c.U = -1; c.lvl = 0; c.base = 0;
+    MtTileUnit u;
+    int cnt = 0, tbase = 0;
+    if (!mt_tile_down(e, c, e.root, 0, 0, MT_TD_FIRST_VIS)) return 0;
+    for (;;) {
+        mt_tile_unit(e, c, u);
+        uint64_t m = u.cand, hit = 0;
+        while (m) {
+            const int t = __builtin_ctzll(m);
+            m &= ~(1ull << t);
+            if (mt_tile_map_has(e, S, wave_at(u.props, t), lab, memo)) hit |= 1ull << t;
+        }
+        if (hit && out) {
+            const int ub = c.base, tb = tbase, c0 = cnt;
+            wave_for(MT_WAVE, [&](int t) MT_LAM {
+                const unsigned long long k = (unsigned long long)c0 + (unsigned long long)__builtin_popcountll(hit & ((1ull << t) - 1ull));
+                if (((hit >> t) & 1ull) && k < room) {      // guards the stores only
+                    const int g = own(u.row, t);
+                    mt_tile_rec r;
+                    r.pos = ub + own(u.pre, t); r.text_pos = tb + own(u.tpre, t); r.row = g; r.prop_set = own(u.props, t);
+                    r.ref_type = own(u.toff, t); r.marker_id = e.row(g).mid - 1; r.pad[0] = 0; r.pad[1] = 0;
+                    out[k] = r;
+                }
+            });
+        }
+        cnt += __builtin_popcountll(hit);
+        tbase += u.tvis;
+        if (!mt_tile_next(e, c, 1, false)) return cnt;
+    }
+}
 
 template <class Eng>
 MT_HD void mt_query_run(Eng& e, const MtState& S, const MtQuery* q, uint32_t q0, uint32_t q1, MtQueryOut* out) {
+    MtTileMemo memo; memo.lab = -1; memo.ps = -1; memo.res = false;
     for (uint32_t i = q0; i < q1; i++) {
         const int pos = uni(q[i].pos), ref = uni(q[i].ref), qc = uni(q[i].client);
+        if (ref <= MT_QK_TILE) {                    // tile search: the local view, nothing written to the document
+            const int lab = qc & (MT_QT_PRECEDING - 1);
+            if (ref == MT_QK_TILE) {
+                int op = 0, depth = 0;
+                unsigned long long path = 0;
+                const int s = mt_find_tile_doc(e, S, pos, lab, (qc & MT_QT_PRECEDING) != 0, memo, op, depth, path);
+                mt_query_emit(e, S, out[i], s, 0, op, depth, path, (int)0x80000000);
+            } else {
+                const bool fill = ref == MT_QK_TILE_FILL;
+                const unsigned long long at = fill ? (unsigned long long)(uint32_t)pos : 0ull;
+                const unsigned long long room = (fill && S.t_out && at < S.t_cap) ? S.t_cap - at : 0ull;
+                const int cnt = mt_tile_index_doc(e, S, lab, memo, room ? S.t_out + at : nullptr, room);
+                MtQueryOut& o = out[i];
+                wave_for(16, [&](int k) MT_LAM { ((int*)&o.info)[k] = k == 0 ? cnt : 0; });
+                wave_sync();
+            }
+            continue;
+        }
         // the local view: every sequenced op applied (removals included), as (refSeq = max,
         // a client id no row carries) sees it
         const bool local = ref < 0;
@@ -30,42 +372,14 @@ MT_HD void mt_query_run(Eng& e, const MtState& S, const MtQuery* q, uint32_t q0,
         int off = 0, depth = 0;
         unsigned long long path = 0;
         const int s = e.containing(pos, r, c, off, depth, path);
-        int f[16];
-        for (int k = 0; k < 16; k++) f[k] = 0;
-        unsigned long long tat = 0;
-        int nch = 0, ps = -1;
-        if (s >= 0) {
-            const uint32_t mt = uni(e.row(s).meta);
-            const bool removed = (mt & MT_M_REMOVED) != 0, marker = (mt & MT_M_MARKER) != 0;
-            const int cl = (int)(mt & MT_M_CLIENT);
-            const int op = e.obsPosition(s);
-            ps = uni(e.row(s).props);
-            f[0] = 1; f[1] = off; f[2] = op; f[3] = uni(e.row(s).len); f[4] = uni(e.row(s).seq);
-            f[5] = cl == MT_NONCOLLAB ? -1 : cl;
-            f[6] = removed ? uni(e.row(s).rseq) : (int)0x80000000;
-            f[7] = removed ? (int)uni(e.row(s).rcl) : -1;
-            f[8] = ps; f[9] = marker ? uni(e.row(s).toff) : -1;
-            f[10] = depth; f[11] = (int)(uint32_t)path; f[12] = (int)(uint32_t)(path >> 32);
-            f[13] = s; f[14] = op + off;
-            if (!marker) tat = (unsigned long long)(e.text - S.text) + (unsigned long long)uni(e.row(s).toff);
-            if (ps >= 0) { const int n = uni(e.pset[ps].n); nch = n > MT_PSK ? (n + MT_PSK - 1) / MT_PSK : 1; }
-        } else {
+        int op = 0, resolved = 0;
+        if (s >= 0) op = e.obsPosition(s);
+        else {
             // resolveRemoteClientPosition's fall-through: the end of the remote view maps to the
             // end of the local one
             const int L = e.perspectiveLength(r, c);
-            f[1] = -1; f[2] = -1; f[5] = -1; f[6] = (int)0x80000000; f[7] = -1; f[8] = -1; f[9] = -1; f[13] = -1;
-            f[14] = pos == L ? uni(e.bk(e.root).len) : (int)0x80000000;
+            resolved = pos == L ? uni(e.bk(e.root).len) : (int)0x80000000;
         }
-        MtQueryOut& o = out[i];
-        const auto fv = wave_map(16, [&](int k) MT_LAM { return pick16(f, k); });
-        wave_for(16, [&](int k) MT_LAM { ((int*)&o.info)[k] = own(fv, k); });
-        wave_for(1, [&](int) MT_LAM { o.text_at = tat; o.pad = 0; });
-        // the property map's chunks, one dword per lane (28 dwords a chunk)
-        constexpr int W = (int)(sizeof(MtPSet) / 4);
-        for (int base = 0; base < nch * W; base += MT_WAVE) {
-            const int m = (nch * W - base) < MT_WAVE ? (nch * W - base) : MT_WAVE;
-            wave_for(m, [&](int k) MT_LAM { ((int*)o.ps)[base + k] = ((const int*)(e.pset + ps))[base + k]; });
-        }
-        wave_sync();
+        mt_query_emit(e, S, out[i], s, off, op, depth, path, resolved);
     }
 }

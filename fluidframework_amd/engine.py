@@ -57,6 +57,11 @@ class MtDocCounters(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("ops", "msgs", "ins_units", "rows_rw", "depth", "scoured")]
 
 
+class MtTileLabels(ctypes.Structure):
+    _fields_ = [("n_labels", ctypes.c_uint32), ("key", ctypes.c_uint32), ("n_values", ctypes.c_uint32),
+                ("match", ctypes.c_void_p)]
+
+
 def _bind(lib, prefix: str):
     P, U32, I32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32
 
@@ -124,6 +129,10 @@ def _bind(lib, prefix: str):
         get_containing_segment=f("get_containing_segment", ctypes.c_int,
                                  [P, U32, P, P, P, P, P, ctypes.POINTER(P), ctypes.POINTER(P)]),
         resolve_remote_position=f("resolve_remote_position", ctypes.c_int, [P, U32, P, P, P, P, P]),
+        find_tile=f("find_tile", ctypes.c_int, [P, U32, P, P, P, P, ctypes.POINTER(MtTileLabels), P, ctypes.POINTER(P),
+                                                ctypes.POINTER(P)]),
+        tile_index=f("tile_index", ctypes.c_int, [P, U32, P, P, ctypes.POINTER(MtTileLabels), ctypes.POINTER(P),
+                                                  ctypes.POINTER(P)]),
         set_doc_snapshot_chunk=f("set_doc_snapshot_chunk", ctypes.c_int, [P, U32, P, P]),
         reserve_staging=f("reserve_staging", ctypes.c_int, [P, ctypes.c_uint64]),
         docs_resize=f("docs_resize", ctypes.c_int, [P, U32, P, P]),
@@ -144,6 +153,8 @@ SEG_INFO_FIELDS = ("found", "offset", "obs_pos", "len", "seq", "client", "remove
                    "marker_ref_type", "depth", "path_lo", "path_hi", "row", "resolved", "pad")
 SEG_INFO_DTYPE = np.dtype([(f, np.uint32 if f.startswith("path") else np.int32) for f in SEG_INFO_FIELDS])
 POS_UNDEFINED = -(1 << 31)              # MT_POS_UNDEFINED
+TILE_REC_DTYPE = np.dtype([(f, np.int32) for f in ("pos", "text_pos", "row", "prop_set", "ref_type", "marker_id",
+                                                   "pad0", "pad1")])    # mt_tile_rec
 MT_CHUNK_INFINITY = (1 << 64) - 1      # mt_set_doc_snapshot_chunk: Infinity (one chunk)
 MT_CHUNK_NONE = (1 << 64) - 2          # a size no length is below (0, negative, NaN)
 MT_PARTITION_AUTO = 0xFFFFFFFF         # mt_set_partition: chosen per batch (mt_plan_partition)
@@ -571,6 +582,64 @@ class Engine:
                                                        c.ctypes.data, out.ctypes.data), "mt_resolve_remote_position")
         return out
 
+    # ---- tile search (include/mtgpu.h mt_find_tile / mt_tile_index) ----
+    def _tile_labels(self, label: str) -> MtTileLabels:
+        """mt_tile_labels of one label, built once and kept until the prop table grows."""
+        if self._props_uploaded != len(self.props.sets) or getattr(self, "_tile_nvalues", -1) != len(self.props.values_json):
+            self.upload_props()
+            self._tile_cache, self._tile_nvalues = {}, len(self.props.values_json)
+        t = self._tile_cache.get(label)
+        if t is None:
+            from .batch import TILE_LABELS_KEY
+            m = np.ascontiguousarray(self.props.tile_match([label]))
+            key = self.props.key_ids.get(TILE_LABELS_KEY, 0xFFFFFFFF)
+            t = self._tile_cache[label] = (MtTileLabels(1, key, m.shape[1], m.ctypes.data if m.size else None), m)
+        return t[0]
+
+    def find_tile(self, docs, pos, label: str, preceding=True, json: bool = True):
+        """mt_find_tile: Client.findTile(pos[i], label, preceding[i]) (MT/client.ts:1095-1098) of
+        each query in the local view; pos None / POS_UNDEFINED is an undefined startPos.  Returns
+        (SEG_INFO_DTYPE records filled as containing_segment fills them for the tile's row, with
+        found = 0 for undefined; the markers' JSON texts or None).  This is the raw ABI: it takes
+        no part in the "tile labels annotated" mark of MergeTreeClient.findTile, so on a
+        document whose referenceTileLabels were annotated it answers from the leaves alone,
+        where the reference's answer depends on its stale block caches."""
+        d = _u32(docs)
+        n = len(d)
+        p = _i32([POS_UNDEFINED if x is None else int(x) for x in np.broadcast_to(np.asarray(pos, object), (n,))])
+        fl = np.ascontiguousarray(np.broadcast_to(np.asarray(preceding, bool), (n,)), np.uint8)
+        lab = np.zeros(n, np.uint32)
+        t = self._tile_labels(label)
+        out = np.zeros(n, SEG_INFO_DTYPE)
+        arena, off = ctypes.c_void_p(), ctypes.c_void_p()
+        self._check(self.fn["find_tile"](self.h, n, d.ctypes.data, p.ctypes.data, fl.ctypes.data, lab.ctypes.data,
+                                         ctypes.byref(t), out.ctypes.data, ctypes.byref(arena) if json else None,
+                                         ctypes.byref(off) if json else None), "mt_find_tile")
+        texts = [None] * n
+        if json:
+            offs = np.ctypeslib.as_array(ctypes.cast(off, ctypes.POINTER(ctypes.c_uint64)), (n + 1,)).copy()
+            raw = ctypes.string_at(arena, int(offs[-1])) if offs[-1] else b""
+            texts = [raw[offs[i]:offs[i + 1]].decode("utf-8", "surrogatepass") if out["found"][i] else None
+                     for i in range(n)]
+        return out, texts
+
+    def tile_index(self, docs, label: str):
+        """mt_tile_index: every visible tile of each document carrying `label`, in document order.
+        Returns (TILE_REC_DTYPE records, offsets [n + 1]): document i owns records
+        [off[i], off[i + 1]).  Raw ABI, as find_tile."""
+        d = _u32(docs)
+        n = len(d)
+        lab = np.zeros(n, np.uint32)
+        t = self._tile_labels(label)
+        recs, off = ctypes.c_void_p(), ctypes.c_void_p()
+        self._check(self.fn["tile_index"](self.h, n, d.ctypes.data, lab.ctypes.data, ctypes.byref(t), ctypes.byref(recs),
+                                          ctypes.byref(off)), "mt_tile_index")
+        offs = np.ctypeslib.as_array(ctypes.cast(off, ctypes.POINTER(ctypes.c_uint64)), (n + 1,)).copy()
+        total = int(offs[-1])
+        if not total:
+            return np.zeros(0, TILE_REC_DTYPE), offs
+        return np.frombuffer(ctypes.string_at(recs, total * TILE_REC_DTYPE.itemsize), TILE_REC_DTYPE).copy(), offs
+
     def snapshot(self, docs, msn, seq, legacy: bool = False):
         """SnapshotV1 (or, with legacy, SnapshotLegacy header/body) blobs per document:
         list of (list[bytes], digest)."""
@@ -709,6 +778,7 @@ class MergeTreeClient:
         self.min_seq = 0
         self.longClientId = None
         self.delta_listener = None       # SequenceDoc's sequenceDelta subscription (sequence.py)
+        self.tile_labels_annotated = False   # an annotate naming referenceTileLabels was packed (findTile)
 
     def startOrUpdateCollaboration(self, longClientId, minSeq=0, currentSeq=0, branchId=0):
         self.longClientId = longClientId
@@ -813,6 +883,22 @@ class MergeTreeClient:
             return {"segment": None, "offset": None}
         return {"segment": Segment(info, js, self, self.group.version), "offset": int(info["offset"])}
 
+    def findTile(self, startPos, tileLabel: str, preceding: bool = True):
+        """Client.findTile (client.ts:1095-1098 -> MergeTree.findTile, mergeTree.ts:1752-1778) in
+        the local view: {"tile": Segment, "pos": int} or None.  startPos None is undefined
+        (SharedString.findTile allows it).  Raises MergeTreeError on a document an annotate
+        naming referenceTileLabels was applied to: the reference's answer there depends on
+        block caches that annotateRange leaves stale (mergeTree.ts:2584-2624)."""
+        self.group.flush()
+        self._raise_status()
+        if self.tile_labels_annotated:
+            raise MergeTreeError(f"document {self.doc_id}: referenceTileLabels were annotated; the reference's tile "
+                                 "caches are stale there and findTile is not reproduced")
+        info, js = self.engine.find_tile([self.doc_id], [startPos], tileLabel, bool(preceding))
+        if not info["found"][0]:
+            return None
+        return {"tile": Segment(info[0], js[0], self, self.group.version), "pos": int(info["obs_pos"][0])}
+
     def getPosition(self, segment: Segment) -> int:
         """Client.getPosition (client.ts:306-311): the segment's local position."""
         if segment is None:
@@ -903,6 +989,8 @@ class ClientGroup:
                 c.current_seq = int(m["sequenceNumber"])
                 c.min_seq = max(c.min_seq, int(m["minimumSequenceNumber"]))
             c.pending = []
+            if c.doc_id in bb.tile_annotated:
+                c.tile_labels_annotated = True
             if c.delta_listener is not None:
                 listen.append((c, entries))
             if c.names_uploaded != len(c.names.names):

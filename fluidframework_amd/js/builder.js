@@ -12,6 +12,7 @@ const OP_CUT = 5, OP_COPY = 6, OP_PASTE = 7;          // register ops (include/m
 const F_END = 1, F_MARKER = 2, F_REWRITE = 4, F_SEG_PROPS = 8, F_COMBINE = 16, F_REL1 = 0x20, F_REL2 = 0x40,
     F_MARKER_ID = 0x80;
 const MARKER_ID_KEY = "markerId";   // reservedMarkerIdKey, MT/mergeTree.ts:591
+const TILE_LABELS_KEY = "referenceTileLabels";   // reservedTileLabelsKey, MT/mergeTree.ts:589
 // property values other than interned ids, and value kinds (include/mtgpu.h MT_VAL_*, MT_VK_*)
 const VAL_NULL = -1, VAL_NAN = -2, VAL_UNSUP = -3, VAL_CFRESH = -4, VAL_UNDEF = -5, VAL_THROW = -6, VAL_CONS_BASE = -16;
 const F_CONSENSUS = 2, F_INCR_STRMIN = 8;   // on combining annotates (include/mtgpu.h)
@@ -70,6 +71,26 @@ class PropTable {
     }
     intern(props) {
         return this.internPairs(Object.keys(props).map((k) => [this.keyId(k), this.valueId(props[k])]));
+    }
+    /**
+     * mt_tile_labels.match for `labels`: Uint8Array [labels.length * valueJson.length], 1 where
+     * iterating the value as refHasTileLabel does (MT/mergeTree.ts:600-610) yields the label.
+     * A value that is neither an array nor a string never matches (the reference throws on a
+     * truthy one while it applies the insert, addTile :221-228; a falsy one has no labels).
+     */
+    tileMatch(labels) {
+        const nv = this.valueJson.length;
+        const m = new Uint8Array(labels.length * nv);
+        for (let v = 0; v < nv; v++) {
+            const val = JSON.parse(this.valueJson[v]);
+            if (!Array.isArray(val) && typeof val !== "string") continue;
+            labels.forEach((label, i) => {
+                for (const refLabel of val) {
+                    if (label === refLabel) { m[i * nv + v] = 1; break; }
+                }
+            });
+        }
+        return m;
     }
     /**
      * [combine set, flags] of a remote annotate with a combining op other than "rewrite"
@@ -214,12 +235,16 @@ class BatchBuilder {
         this.props = props; this.names = names;
         this.cols = {}; for (const [n, T] of COLS) this.cols[n] = new Col(T, 1024, shared);
         this.payload = new Col(Uint16Array, 4096, shared); this.docIds = []; this.offsets = [0]; this.rel = [];
+        // documents an annotate naming referenceTileLabels was packed for: the reference's block
+        // tile caches go stale there (annotateRange runs no blockUpdate, mergeTree.ts:2584-2624),
+        // so MergeTreeClient.findTile refuses them
+        this.tileAnnotated = new Set();
     }
     /** Empty again, keeping the columns' memory (a worker's builder, batch after batch). */
     reset(props) {
         this.props = props;
         for (const k in this.cols) this.cols[k].n = 0;
-        this.payload.n = 0; this.docIds = []; this.offsets = [0]; this.rel = [];
+        this.payload.n = 0; this.docIds = []; this.offsets = [0]; this.rel = []; this.tileAnnotated = new Set();
     }
     get nOps() { return this.cols.type.n; }
     /** op.pos{k}, or op.relativePos{k} as an index into rel (getValidOpRange, client.ts:506-523). */
@@ -285,6 +310,9 @@ class BatchBuilder {
             if (op.type === OP_ANNOTATE) {
                 // segmentPropertiesManager.ts:55-56: rewrite = op && op.name === "rewrite"; any other
                 // truthy combiningOp combines (properties.ts:24-62)
+                if (op.props && typeof op.props === "object" && TILE_LABELS_KEY in op.props && this.docIds.length) {
+                    this.tileAnnotated.add(this.docIds[this.docIds.length - 1]);
+                }
                 const cop = op.combiningOp, combine = !!cop && cop.name !== "rewrite";
                 if (cop && !combine) fl |= F_REWRITE;
                 if (op.props && typeof op.props === "object" && MARKER_ID_KEY in op.props) { bad(); return; }   // re-keyed marker ids
@@ -402,5 +430,5 @@ class BatchBuilder {
 
 module.exports = { VAL_NULL, VAL_NAN, VAL_UNSUP, VAL_CFRESH, VAL_UNDEF, VAL_THROW, VAL_CONS_BASE, VK_NUM, VK_SEQM1,
     OP_INSERT, OP_REMOVE, OP_ANNOTATE, OP_NOOP, OP_GROUP, OP_UNSUPPORTED, OP_CUT, OP_COPY, OP_PASTE,
-    F_END, F_MARKER, F_REWRITE, F_SEG_PROPS, F_COMBINE, F_REL1, F_REL2, F_MARKER_ID, MARKER_ID_KEY, arrayIndex,
+    F_END, F_MARKER, F_REWRITE, F_SEG_PROPS, F_COMBINE, F_REL1, F_REL2, F_MARKER_ID, MARKER_ID_KEY, TILE_LABELS_KEY, arrayIndex,
     matchClassKey, PropTable, ClientNames, mergeTreeMembers, COLS, Col, BatchBuilder };

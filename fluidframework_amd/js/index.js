@@ -27,7 +27,7 @@ const path = require("path");
 const addon = require(process.env.MTGPU_NAPI || path.join(__dirname, "mtgpu.node"));
 
 const { VAL_NAN, VAL_UNDEF, VAL_CONS_BASE, OP_INSERT, OP_REMOVE, OP_ANNOTATE, OP_NOOP, OP_GROUP, OP_UNSUPPORTED, OP_CUT, OP_COPY, OP_PASTE,
-    F_END, F_MARKER, F_REWRITE, F_SEG_PROPS, F_COMBINE, F_REL1, F_REL2, F_MARKER_ID, MARKER_ID_KEY, arrayIndex,
+    F_END, F_MARKER, F_REWRITE, F_SEG_PROPS, F_COMBINE, F_REL1, F_REL2, F_MARKER_ID, MARKER_ID_KEY, TILE_LABELS_KEY, arrayIndex,
     matchClassKey, PropTable, ClientNames, mergeTreeMembers, BatchBuilder } = require("./builder.js");
 const STATUS = {
     0x01: "ASSERT_SEQ", 0x02: "ASSERT_MSN", 0x04: "INSERT_FAILED", 0x08: "UNSUPPORTED",
@@ -266,6 +266,46 @@ class Engine {
             return o;
         });
     }
+    /** mt_tile_labels of one label, built once and kept until the prop table grows. */
+    tileLabels(label) {
+        this.uploadProps();
+        if (this.tileValues !== this.props.valueJson.length) { this.tileCache = new Map(); this.tileValues = this.props.valueJson.length; }
+        let t = this.tileCache.get(label);
+        if (t === undefined) {
+            const key = this.props.keyIds.get(TILE_LABELS_KEY);
+            t = { key: key === undefined ? 0xFFFFFFFF : key, nValues: this.tileValues, match: this.props.tileMatch([label]) };
+            this.tileCache.set(label, t);
+        }
+        return t;
+    }
+    /**
+     * mt_find_tile: Client.findTile(pos[i], label, preceding[i]) of each query in the local view
+     * (pos undefined: an undefined startPos); records as containingSegment's, found 0 for
+     * undefined.  The raw ABI: it takes no part in MergeTreeClient.findTile's "tile labels
+     * annotated" mark.
+     */
+    findTile(docs, pos, label, preceding) {
+        const t = this.tileLabels(label);
+        const { info, json } = addon.findTile(this.h, Uint32Array.from(docs),
+            Int32Array.from(pos, (p) => (p === undefined ? -(2 ** 31) : p)), Uint8Array.from(preceding, (p) => (p ? 1 : 0)),
+            new Uint32Array(docs.length), t.key, t.nValues, t.match);
+        const F = ["found", "offset", "obsPos", "len", "seq", "client", "removedSeq", "removedClient", "propSet",
+            "markerRefType", "depth", "pathLo", "pathHi", "row", "resolved"];
+        return json.map((j, i) => {
+            const o = { json: j };
+            F.forEach((f, k) => { o[f] = info[16 * i + k]; });
+            return o;
+        });
+    }
+    /**
+     * mt_tile_index: every visible tile of each document carrying `label`, in document order:
+     * { recs: Int32Array (8 per record: pos, textPos, row, propSet, refType, markerId, 0, 0),
+     * off: record offsets, docs.length + 1 }.  Raw ABI, as findTile.
+     */
+    tileIndex(docs, label) {
+        const t = this.tileLabels(label);
+        return addon.tileIndex(this.h, Uint32Array.from(docs), new Uint32Array(docs.length), t.key, t.nValues, t.match);
+    }
     updateSeq(docs, msn, seq) { addon.updateSeq(this.h, Uint32Array.from(docs), Int32Array.from(msn), Int32Array.from(seq)); }
     snapshot(docs, msn, seq, legacy = false) {
         return (legacy ? addon.snapshotLegacy : addon.snapshotV1)(this.h, Uint32Array.from(docs), Int32Array.from(msn),
@@ -305,6 +345,7 @@ class MergeTreeClient {
         this.pending = []; this.names = new ClientNames();
         this.currentSeq = 0; this.minSeq = 0; this.longClientId = undefined;
         this.deltaListener = null;                  // SequenceChannel's sequenceDelta subscription
+        this.tileLabelsAnnotated = false;           // an annotate naming referenceTileLabels was packed (findTile)
     }
     startOrUpdateCollaboration(longClientId, minSeq = 0, currentSeq = 0) {
         this.longClientId = longClientId;
@@ -405,6 +446,9 @@ class MergeTreeClient {
     getContainingSegment(pos) {
         const q = this.query(pos, 0, undefined);
         if (!q.found) return { segment: undefined, offset: undefined };
+        return { segment: this.segmentOf(q), offset: q.offset };
+    }
+    segmentOf(q) {
         const j = JSON.parse(q.json);
         const shortOf = (i) => (i < 0 ? -2 : i + 1);                // NonCollabClient = -2
         const seg = {
@@ -417,7 +461,25 @@ class MergeTreeClient {
         if (typeof j === "string") seg.text = j;
         else if (j.marker) seg.refType = j.marker.refType;
         else seg.text = j.text;
-        return { segment: seg, offset: q.offset };
+        return seg;
+    }
+    /**
+     * Client.findTile (client.ts:1095-1098; MergeTree.findTile, mergeTree.ts:1752-1778) in the
+     * local view: { tile, pos } or undefined; the tile is a copy as getContainingSegment's.
+     * Throws on a document an annotate naming referenceTileLabels was applied to: the
+     * reference's answer there depends on block caches annotateRange leaves stale
+     * (mergeTree.ts:2584-2624).
+     */
+    findTile(startPos, tileLabel, preceding = true) {
+        this.group.flush();
+        this.checkStatus();
+        if (this.tileLabelsAnnotated) {
+            throw new Error(`document ${this.docId}: referenceTileLabels were annotated; the reference's tile caches ` +
+                "are stale there and findTile is not reproduced");
+        }
+        const q = this.group.engine.findTile([this.docId], [startPos], tileLabel, [preceding])[0];
+        if (!q.found) return undefined;
+        return { tile: this.segmentOf(q), pos: q.obsPos };
     }
     /** Client.getPosition (client.ts:306-311) of a segment copy from getContainingSegment. */
     getPosition(segment) {
@@ -499,6 +561,7 @@ class ClientGroup {
             bb.beginDoc(c.docId);
             const entries = c.pending.map((m) => [m, bb.addMessage(m)]);
             c.pending = [];
+            if (bb.tileAnnotated.has(c.docId)) c.tileLabelsAnnotated = true;
             if (c.deltaListener) listen.push([c, entries]);
             if (c.namesUploaded !== c.names.names.length) {     // snapshot "client" fields use long ids
                 addon.setDocClientNames(this.engine.h, c.docId, c.names.names.map((n) => JSON.stringify(n)));

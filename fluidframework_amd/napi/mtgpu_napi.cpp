@@ -512,6 +512,69 @@ napi_value GetContainingSegment(napi_env env, napi_callback_info info) {
     return o;
 }
 
+// The mt_tile_labels of (key, nValues, match: Uint8Array [nLabels * nValues]) at argv[k..k+2].
+static bool tile_labels(napi_env env, const napi_value* argv, mt_tile_labels* T) {
+    const uint8_t* match; size_t nm;
+    uint32_t key = 0, nv = 0;
+    napi_get_value_uint32(env, argv[0], &key); napi_get_value_uint32(env, argv[1], &nv);
+    if (!typed(env, argv[2], napi_uint8_array, &match, &nm)) return false;
+    if (nv && nm % nv) { napi_throw_range_error(env, nullptr, "match is not a multiple of nValues long"); return false; }
+    T->n_labels = nv ? (uint32_t)(nm / nv) : 1; T->key = key; T->n_values = nv; T->match = match;
+    return true;
+}
+// findTile(ctx, docs, pos, preceding: Uint8Array, label: Uint32Array, key, nValues, match) ->
+// {info, json} as getContainingSegment's (mt_find_tile)
+napi_value FindTile(napi_env env, napi_callback_info info) {
+    napi_value argv[8];
+    if (!get_args(env, info, 8, argv)) return nullptr;
+    mt_ctx* c = get_ctx(env, argv[0]); if (!c) return nullptr;
+    const uint32_t* docs; const int32_t* pos; const uint8_t* fl; const uint32_t* lab; size_t n, n1, n2, n3;
+    if (!typed(env, argv[1], napi_uint32_array, &docs, &n) || !typed(env, argv[2], napi_int32_array, &pos, &n1) ||
+        !typed(env, argv[3], napi_uint8_array, &fl, &n2) || !typed(env, argv[4], napi_uint32_array, &lab, &n3)) return nullptr;
+    if (n1 < n || n2 < n || n3 < n) { napi_throw_range_error(env, nullptr, "pos/preceding/label shorter than docs"); return nullptr; }
+    mt_tile_labels T;
+    if (!tile_labels(env, argv + 5, &T)) return nullptr;
+    std::vector<mt_seg_info> out(n + 1);
+    const char* arena = nullptr; const uint64_t* off = nullptr;
+    int rc = mt_find_tile(c, (uint32_t)n, docs, pos, fl, lab, &T, out.data(), &arena, &off);
+    if (rc) return throw_rc(env, c, rc, "mt_find_tile");
+    napi_value o, js;
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "info", make_i32(env, (const int32_t*)out.data(), 16 * n));
+    NAPI_OK(napi_create_array_with_length(env, n, &js));
+    for (size_t i = 0; i < n; i++) {
+        napi_value s;
+        if (out[i].found) napi_create_string_utf8(env, arena + off[i], (size_t)(off[i + 1] - off[i]), &s);
+        else napi_get_null(env, &s);
+        napi_set_element(env, js, (uint32_t)i, s);
+    }
+    napi_set_named_property(env, o, "json", js);
+    return o;
+}
+// tileIndex(ctx, docs, label: Uint32Array, key, nValues, match) -> {recs: Int32Array (8 per
+// mt_tile_rec), off: Float64Array (docs + 1)} (mt_tile_index)
+napi_value TileIndex(napi_env env, napi_callback_info info) {
+    napi_value argv[6];
+    if (!get_args(env, info, 6, argv)) return nullptr;
+    mt_ctx* c = get_ctx(env, argv[0]); if (!c) return nullptr;
+    const uint32_t* docs; const uint32_t* lab; size_t n, n1;
+    if (!typed(env, argv[1], napi_uint32_array, &docs, &n) || !typed(env, argv[2], napi_uint32_array, &lab, &n1)) return nullptr;
+    if (n1 < n) { napi_throw_range_error(env, nullptr, "label shorter than docs"); return nullptr; }
+    mt_tile_labels T;
+    if (!tile_labels(env, argv + 3, &T)) return nullptr;
+    const mt_tile_rec* recs = nullptr; const uint64_t* off = nullptr;
+    int rc = mt_tile_index(c, (uint32_t)n, docs, lab, &T, &recs, &off);
+    if (rc) return throw_rc(env, c, rc, "mt_tile_index");
+    napi_value o, ab, ta; void* d = nullptr;
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "recs", make_i32(env, (const int32_t*)recs, 8 * (size_t)off[n]));
+    napi_create_arraybuffer(env, 8 * (n + 1), &d, &ab);
+    for (size_t i = 0; i <= n; i++) ((double*)d)[i] = (double)off[i];
+    napi_create_typedarray(env, napi_float64_array, n + 1, ab, 0, &ta);
+    napi_set_named_property(env, o, "off", ta);
+    return o;
+}
+
 // snapshotV1(ctx, docs, msn, seq) -> [{blobs: [header, body_0, ...], digest: BigInt}]
 // snapshotLegacy(ctx, docs, msn, seq) -> [{blobs: [header(, body)], digest: BigInt}]
 static napi_value snapshot_blobs(napi_env env, napi_callback_info info, bool legacy) {
@@ -717,7 +780,7 @@ napi_value GrowStats(napi_env env, napi_callback_info info) {
 }
 
 const napi_property_attributes kAttr = (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable);
-// The growth calls are callable but not enumerated: Object.keys(addon) stays the surface the
+// The growth and tile-search calls are callable but not enumerated: Object.keys(addon) stays the surface the
 // hosts were written against.
 const napi_property_attributes kQuiet = (napi_property_attributes)(napi_writable | napi_configurable);
 
@@ -754,6 +817,8 @@ napi_value Init(napi_env env, napi_value exports) {
         {"docCaps", nullptr, DocCaps, nullptr, nullptr, nullptr, kQuiet, nullptr},
         {"docOccupancy", nullptr, DocOccupancy, nullptr, nullptr, nullptr, kQuiet, nullptr},
         {"growStats", nullptr, GrowStats, nullptr, nullptr, nullptr, kQuiet, nullptr},
+        {"findTile", nullptr, FindTile, nullptr, nullptr, nullptr, kQuiet, nullptr},
+        {"tileIndex", nullptr, TileIndex, nullptr, nullptr, nullptr, kQuiet, nullptr},
     };
     napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
     return exports;

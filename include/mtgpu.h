@@ -575,6 +575,71 @@ int  mt_get_containing_segment(mt_ctx* ctx, uint32_t n, const uint32_t* doc_ids,
 int  mt_resolve_remote_position(mt_ctx* ctx, uint32_t n, const uint32_t* doc_ids, const int32_t* pos,
                                 const int32_t* ref_seq, const int32_t* client, int32_t* out_pos);
 
+/*
+ * Tile search on the current state of replayed documents, in the local (observer) view.
+ *   Client.findTile(startPos, tileLabel, preceding)  MT/client.ts:1095-1098
+ *   MergeTree.findTile        MT/mergeTree.ts:1752-1778 (local client: nodeLength :1653-1659)
+ *   search / searchBlock      :1780-1820, tileShift :1009-1032, recordTileStart :993-1007
+ *   backwardSearch            :1822-1866
+ *   the blocks' tile caches   :2770-2789, addNodeReferences :276-334, refHasTileLabel :594-610
+ * Rows are the document's segments in order, removed ones included; a row's start is the sum
+ * of the visible lengths before it; L is the observer's length.  A row matches when it is a
+ * marker with refType & 1 (ReferenceType.Tile) whose "referenceTileLabels" value yields the
+ * label (mt_tile_labels.match).
+ *   preceding:      the visible matching row with the largest start <= pos (the last visible
+ *                   match when pos >= L).  A removed row never answers.
+ *   not preceding:  pos > L: undefined.  Otherwise the leaf is the last row whose start is
+ *                   <= pos (`pos >= segpos`, :1841-1855, has no length test, nor has
+ *                   recordTileStart): if it matches it is the answer even when it is removed;
+ *                   otherwise the first visible matching row to its right.  For pos < L that
+ *                   is the visible match with the smallest start >= pos.  For pos == L the leaf
+ *                   is the document's last row: the answer if it matches, visible (at L - 1)
+ *                   or removed (at L), else undefined.
+ *   pos MT_POS_UNDEFINED (SharedString.findTile allows it, sequence/src/sharedString.ts:203):
+ *                   every comparison is false and no leaf is taken: preceding gives the last
+ *                   visible match, not preceding the first.
+ * A negative pos is MT_E_INVALID.  The rule was derived by reading the reference, which could
+ * not be executed (client.spec.ts:28-233 pins seven cases; the pos == L behaviour rests on
+ * :1841-1855 and :993-1007 alone).
+ * Not reproduced: annotateRange maps its leaves without a `post` action (:2584-2624), so no
+ * blockUpdate runs, and after an annotate that sets, changes or deletes "referenceTileLabels"
+ * the reference's block caches are stale until another op passes that way: its answers then
+ * depend on history.  These calls answer from the leaves alone; a caller that has applied such
+ * an annotate to a document must keep that document's tile searches on the reference Client.
+ * A "referenceTileLabels" value that is neither an array, a string nor falsy makes the
+ * reference throw while it applies the insert (addTile :221-228); here it never matches.
+ *
+ * mt_tile_labels: which interned property values yield which labels.  match[l * n_values + v]
+ * is 1 where iterating value v as JS for..of does (an array's elements; a string's code
+ * points) yields an element === label l.  Labels are indices into the caller's own list.
+ */
+typedef struct mt_tile_labels {
+    uint32_t n_labels;
+    uint32_t key;           /* id of "referenceTileLabels" among the prop table's keys;
+                               0xFFFFFFFF: absent, nothing matches                         */
+    uint32_t n_values;      /* must equal the uploaded prop table's n_values               */
+    const uint8_t* match;   /* [n_labels * n_values]                                       */
+} mt_tile_labels;
+#define MT_TILE_PRECEDING 1u
+/* Query i: findTile(pos[i], label[i], flags[i] & MT_TILE_PRECEDING) of document doc_ids[i];
+ * one document's queries run in order in one wave.  out[i] is filled as a containing-segment
+ * query that found the tile's row would fill it: obs_pos = resolved = the tile's pos, offset 0,
+ * the path, depth, row and property set; found = 0 (resolved MT_POS_UNDEFINED): undefined.
+ * json_arena / json_off as mt_get_containing_segment's.  Read-only; documents whose status
+ * word is set are searched as they stand (callers read mt_doc_status, as for
+ * mt_get_containing_segment). */
+int  mt_find_tile(mt_ctx* ctx, uint32_t n, const uint32_t* doc_ids, const int32_t* pos,
+                  const uint8_t* flags, const uint32_t* label, const mt_tile_labels* labels,
+                  mt_seg_info* out, const char** json_arena, const uint64_t** json_off);
+/* Every visible matching tile of each document, in document order: document i's records are
+ * recs[rec_off[i] .. rec_off[i+1]), in a library-owned array valid until the next call.
+ * pos: the tile's start (findTile's pos); text_pos: the visible non-marker units before it
+ * (its index in mt_get_text's string); marker_id: the per-document index of its markerId,
+ * -1 none.  Two device passes over the same scan: count, then fill. */
+typedef struct mt_tile_rec { int32_t pos, text_pos, row, prop_set, ref_type, marker_id, pad[2]; } mt_tile_rec;
+int  mt_tile_index(mt_ctx* ctx, uint32_t n, const uint32_t* doc_ids, const uint32_t* label,
+                   const mt_tile_labels* labels, const mt_tile_rec** recs, const uint64_t** rec_off);
+
 /* Client long-id strings (JSON literals) by per-document client index; used for
  * the snapshot's "client"/"removedClient" fields (snapshotV1.ts:229, :237). */
 int  mt_set_client_names(mt_ctx* ctx, uint32_t n, const char* const* client_json);
