@@ -163,7 +163,10 @@ enum { MT_RES_HBM = 0, MT_RES_LDS = 1, MT_RES_BLK = 2, MT_RES_BIG = 3, MT_RES_BL
 // Range-op events (host-emulation diagnostic builds only, -DMT_EVRANGE): 0 range ops, 1 applied
 // in the start walk's leaf visit (rangeLeaf), 2 start and end boundary in one leaf block,
 // 3 of those the block had no room for the splits, 4 of those refused for another reason
-// (client id, side-list overlap, delta capture, rows, window), 5 rows split by rangeLeaf.
+// (client id, side-list overlap, delta capture, rows, window), 5 rows split by rangeLeaf,
+// 6 inserts whose right half and new row entered the leaf block together (MT_INSERT_LEAF) in the
+// low 32 bits, of those the block split in the high 32 bits, 7 range ops of slot 3 that rangeLeaf
+// applied all the same, splitting the block (MT_LEAF_SPLIT).  Slot 1 counts none of slot 7.
 #if defined(MT_EVRANGE)
 #define MT_EVR(i, v) prof[i] += (unsigned long long)(v)
 #else
@@ -470,6 +473,12 @@ struct __attribute__((aligned(16), may_alias)) MtQ16a { uint32_t x, y, z, w; };
 #ifndef MT_RANGE_LEAF
 #define MT_RANGE_LEAF 1               // opRange: a range inside one leaf block is applied in the start walk's visit
 #endif
+#ifndef MT_LEAF_SPLIT
+#define MT_LEAF_SPLIT 0               // rangeLeaf: also where the right halves split the leaf block (off: DESIGN.md §8)
+#endif
+#ifndef MT_INSERT_LEAF
+#define MT_INSERT_LEAF 1              // opInsert: a split row's right half and the new row enter their leaf block together
+#endif
 #ifndef MT_GT_CH
 #define MT_GT_CH 4                  // gatherText: 64-unit chunks loaded before any is stored
 #endif
@@ -707,6 +716,7 @@ template <int RES, bool FULL = true> struct MtEngT {
     bool bpOn;                          // MT_RES_BIG: the LDS parent cache is kept
     int& nCol = mt_cold_v.ncol;         // rows gathered by rangeMap(MT_MAP_COLLECT) at the register arena's tail
     int landB;                          // leaf block the last insertAtPath linked its node under
+    int pendR;                          // walk(..., defer): the right half the walk cut and left for opInsert to link (-1: none)
     int rfN; int*& rfHbm = mt_cold_v.rfhbm;   // recycled-row stack: depth, HBM home between runs
     int& blkFreeN = mt_cold_v.blkfreen;       // blocks on the free list
     int &heapHW = mt_cold_v.hw[0], &winHW = mt_cold_v.hw[1];   // high-water marks of heapN / winN
@@ -749,7 +759,7 @@ template <int RES, bool FULL = true> struct MtEngT {
         c_ops = c_msgs = c_ins = c_rows = c_depth = c_scour = 0;
         nU = 0; uValid = false; uRef = -1; uCli = -1;
         heapTop = heapN > 0 ? uni(heap[1].maxSeq) : 0x7FFFFFFF;     // HBM home: bind precedes toLds
-        lastL = 0; lastIdx = 0; lastSplit = false; gcEpoch = 0; htOk = false; hlistN = 0; htOn = pfOn = false; mwSeq = 0; bpOn = false;
+        lastL = 0; lastIdx = 0; lastSplit = false; pendR = -1; gcEpoch = 0; htOk = false; hlistN = 0; htOn = pfOn = false; mwSeq = 0; bpOn = false;
         for (int i = 0; i < 4; i++) mt_cold_v.pcKey[i] = -1;
         rfHbm = st.hold + (size_t)d * MT_RFL; rfN = uni(h.rfN); blkFreeN = uni(h.blkFreeN);
         heapHW = uni(h.heapHW); winHW = uni(h.winHW); ovxN = uni(h.ovxN);
@@ -1959,7 +1969,17 @@ template <int RES, bool FULL = true> struct MtEngT {
     // Insert `node` at child index idx of path level L, splitting full blocks
     // 4/4 upward (insertingWalk :2465-2489, split :2495-2508, updateRoot :1868).
     // `delta` = observer length added under the path (0 for a row split).
-    MT_HD void insertAtPath(int L, int idx, int node, int delta) {
+    // PAIR (leaf level): two rows go in at once, `node` at idx and `half` (>= 0) at hidx > idx,
+    // both indices as in the finished child list.  MT_INSERT_LEAF: an inserted row and, right
+    // behind it, the right half of the row split at its position.  MT_LEAF_SPLIT: the right
+    // halves of a range op's two boundaries.  The block is left as the two insertions one after
+    // the other leave it, the one at `late` coming second: a block of 6 children splits 4/4 once
+    // both are in; a block of 7 splits 4/4 under the first alone, and the second then joins the
+    // block that its walk finds, which is the one holding its left neighbour (the old block, at
+    // its end, when that neighbour is its last child).  landB: the block of the child at `watch`.
+    template <bool PAIR = false>
+    MT_HD void insertAtPath(int L, int idx, int node, int delta, int half = -1, int hidx = 0, int late = 0, int watch = 0) {
+        if (!PAIR) watch = idx;
         bool first = true;
         for (;;) {
             const int B = uni(sc->pathB[L]);
@@ -1967,15 +1987,28 @@ template <int RES, bool FULL = true> struct MtEngT {
             auto cur = blkLoad(B, h);
             auto prv = wave_from8<-1>(cur);
             const int nd = node, ix = idx;
+            const bool two = PAIR && first && half >= 0;
             // branch-free blend: a ?: chain here gets turned into a select of
             // closure-field addresses, which forces the closure into scratch
-            auto nc = wave_map(8, [=](int i) MT_LAM {
-                const int a = own(cur, i), b = own(prv, i);
-                const int lt = -(int)(i < ix), eq = -(int)(i == ix);
-                return (a & lt) | (nd & eq) | (b & ~(lt | eq));
-            });
-            const int n1 = h.n + 1;
-            setChildParent(h.height, node, B);
+            LaneArr<int> nc;
+            if (two) {                                       // lanes 0..8: children, node at ix, half at hx
+                auto prv2 = wave_from8<-2>(cur);
+                const int hf = half, hx = hidx;
+                nc = wave_map(9, [=](int i) MT_LAM {
+                    const int a = own(cur, i), b = own(prv, i), b2 = own(prv2, i);
+                    const int lt = -(int)(i < ix), eq = -(int)(i == ix), mid = -((int)(i > ix) & (int)(i < hx)),
+                              e2 = -(int)(i == hx);
+                    return (a & lt) | (nd & eq) | (b & mid) | (hf & e2) | (b2 & ~(lt | eq | mid | e2));
+                });
+            } else {
+                nc = wave_map(8, [=](int i) MT_LAM {
+                    const int a = own(cur, i), b = own(prv, i);
+                    const int lt = -(int)(i < ix), eq = -(int)(i == ix);
+                    return (a & lt) | (nd & eq) | (b & ~(lt | eq));
+                });
+            }
+            const int n1 = h.n + (two ? 2 : 1);
+            setChildParent(h.height, node, B);                // (a half has its block as parent since it was cut)
             if (first) landB = B;
             if (n1 < MT_MAXN) {
                 wave_for(8, [&](int i) MT_LAM { bk(B).c[i] = i < n1 ? own(nc, i) : -1; });
@@ -1988,19 +2021,21 @@ template <int RES, bool FULL = true> struct MtEngT {
             MT_EV(6, 1);
             const int NB = allocBlock();
             if (NB < 0) return;
-            auto hi = wave_from8<4>(nc);
+            // children kept: 4, or 5 of 9 when the second row follows the first one's split into the old block
+            const int kb = (two && n1 == MT_MAXN + 1 && late <= 4) ? 5 : 4, kn = two ? n1 - kb : 4;
+            auto hi = kb == 5 ? wave_from8<5>(nc) : wave_from8<4>(nc);
             wave_for(8, [&](int i) MT_LAM {
-                bk(NB).c[i] = i < 4 ? own(hi, i) : -1;
-                bk(B).c[i] = i < 4 ? own(nc, i) : -1;
+                bk(NB).c[i] = i < kn ? own(hi, i) : -1;
+                bk(B).c[i] = i < kb ? own(nc, i) : -1;
             });
-            bk(NB).n = 4; bk(NB).height = h.height; bk(NB).scour = -1; bk(NB).parent = h.parent;
+            bk(NB).n = kn; bk(NB).height = h.height; bk(NB).scour = -1; bk(NB).parent = h.parent;
             bpPut(NB, h.parent);
-            bk(B).n = 4;
-            wave_for(4, [&](int i) MT_LAM { setChildParent(h.height, own(hi, i), NB); });
-            if (first && ix >= 4) landB = NB;
+            bk(B).n = kb;
+            wave_for(kn, [&](int i) MT_LAM { setChildParent(h.height, own(hi, i), NB); });
+            if (first && watch >= kb) landB = NB;
             first = false;
             wave_sync();
-            const int nbLen = sumObs(NB, 4, h.height), bLen = sumObs(B, 4, h.height);
+            const int nbLen = sumObs(NB, kn, h.height), bLen = sumObs(B, kb, h.height);
             bk(NB).len = nbLen; bk(B).len = bLen;
             if (L == 0) {
                 const int R = allocBlock();
@@ -2043,7 +2078,10 @@ template <int RES, bool FULL = true> struct MtEngT {
         const uint32_t mj = wave_at(meta, j), mje = je >= 0 ? wave_at(meta, je) : 0u;
         const int s1 = (int)(pj > 0) & (int)!(mj & MT_M_MARKER), s2 = (int)(pje > 0) & (int)!(mje & MT_M_MARKER);
         const int ns = s1 + s2;                              // je == j with both: row j becomes three
-        if (n + ns >= MT_MAXN) { MT_EVR(3, 1); return false; }
+        // No room for the halves: the block splits, by the rule of the two walks' insertions one
+        // after the other (insertAtPath<true>), and the new block goes up the path as ever.
+        const bool room = n + ns < MT_MAXN;
+        if (!room) { MT_EVR(3, 1); if (!MT_LEAF_SPLIT) return false; }
         // covered rows: rangeMap's condition (a split row is covered in its half inside the range)
         const auto cov = wave_map(n, [&](int i) MT_LAM {
             const int q = own(pre, i), l = own(len, i);
@@ -2058,11 +2096,14 @@ template <int RES, bool FULL = true> struct MtEngT {
         })) != 0;
         const int w1 = s1 & (int)((mj & MT_M_INWIN) != 0), w2 = s2 & (int)((mje & MT_M_INWIN) != 0);
         const int nadd = wave_count(add);
-        if (side || rfN + ((int)S.rowCap - rowTop) < ns || winN + w1 + w2 + nadd > (int)S.winCap) {
-            MT_EVR(4, 1);
+        // (a split may take a block per level of the path and one for a new root)
+        const bool blocks = room || blkFreeN + ((int)blkCap - blkTop) >= L + 2;
+        if (side || rfN + ((int)S.rowCap - rowTop) < ns || winN + w1 + w2 + nadd > (int)S.winCap || !blocks) {
+            if (room) { MT_EVR(4, 1); }
             return false;
         }
-        MT_EVR(1, 1); MT_EVR(5, ns); MT_EV2(5, ns); MT_EV2(7, 1);
+        if (room) { MT_EVR(1, 1); } else { MT_EVR(7, 1); }
+        MT_EVR(5, ns); MT_EV2(5, ns); MT_EV2(7, 1);
         int n1 = -1, n2 = -1;                                 // right halves, in the two walks' order
         if (s1) n1 = allocRow();
         if (s2) n2 = allocRow();
@@ -2129,27 +2170,46 @@ template <int RES, bool FULL = true> struct MtEngT {
             winN += nadd;
         }
         if (winN > winHW) winHW = winN;
-        if (ns) {                                            // the block's children, once
+        bool firstKept = true;                               // the first covered row stays in B
+        int first2 = -1;                                     // first covered row of the new block
+        if (!room) {
+            // Both blocks' children, lengths and parents, and the ancestors, from the rows as
+            // stored.  kb: the children B keeps, by insertAtPath's rule (the end's half second).
+            const int kb = (ns == 2 && n == MT_MAXN - 1 && je + 2 <= 4) ? 5 : 4;
+            const auto inNew = wave_map(n, [&](int i) MT_LAM {
+                const int f = ((int)(i == j) & s1) ? j + 1 : i + (s1 & (int)(i > j)) + (s2 & (int)(i > je));
+                return (bool)((int)own(cov, i) & (int)(f >= kb));
+            });
+            first2 = wave_first(inNew);
+            firstKept = first2 != first;
+            wave_sync();
+            if (ns == 2) insertAtPath<true>(L, j + 1, n1, obsDelta, n2, je + 2, je + 2, MT_MAXN);
+            else insertAtPath<true>(L, s1 ? j + 1 : je + 1, s1 ? n1 : n2, obsDelta, -1, 0, 0, MT_MAXN);   // landB: the new block
+            wave_sync();
+        } else if (ns) {                                     // the block's children, once
             wave_for(n, [&](int i) MT_LAM { bk(B).c[i + (s1 & (int)(i > j)) + (s2 & (int)(i > je))] = own(ch, i); });
             if (s1) bk(B).c[j + 1] = n1;
             if (s2) bk(B).c[je + 1 + s1] = n2;
             bk(B).n = n + ns;
             landB = B;
         }
-        if (rem) {
+        if (rem && room) {
             bk(B).len = h.len + obsDelta;
             if (L > 0 && obsDelta != 0) {                    // ancestors on the path: one lane per level
                 wave_for(L, [&](int l) MT_LAM { const int pb = sc->pathB[l]; bk(pb).len = bk(pb).len + obsDelta; });
                 wave_sync();
             }
         }
-        if (first >= 0) {
-            const bool half = first == j && s1;
-            const uint32_t m0 = half ? mj & ~MT_M_HREF : wave_at(meta, first);
-            addToLRUSetKnown(half ? n1 : wave_at(ch, first), sq, B, rem ? m0 | MT_M_REMOVED | MT_M_INWIN : m0);
-        }
+        // the LRU entry of each block's first covered row, as rangeMap makes them block by block
+        auto lru = [&](int i, int blk) MT_LAM {
+            const bool half = i == j && s1;
+            const uint32_t m0 = half ? mj & ~MT_M_HREF : wave_at(meta, i);
+            addToLRUSetKnown(half ? n1 : wave_at(ch, i), sq, blk, rem ? m0 | MT_M_REMOVED | MT_M_INWIN : m0);
+        };
+        if (first >= 0 && firstKept) lru(first, B);
+        if (!room && first2 >= 0) lru(first2, landB);
         c_rows += 2u * (uint32_t)(ns + nact);
-        lastL = L; lastSplit = false; uValid = false;
+        lastL = L; lastSplit = !room; uValid = false;
         lastIdx = je < 0 ? n + s1 : (s2 ? je + 1 + s1 : je + (s1 & (int)(je > j)));
         return true;
     }
@@ -2158,8 +2218,10 @@ template <int RES, bool FULL = true> struct MtEngT {
     // valid, U unchanged): the root descent would pick the same children down to there.
     // MT_WALK_RANGE: a split walk to the start of the range op [pos, rEnd) (mode, sequence
     // number, property set and mode as opRange's): MT_W_RANGED if rangeLeaf applied the whole op.
+    // `defer` (MT_WALK_SPLIT ahead of an insert): a split row's right half is written but left
+    // for the caller to link (pendR; the landing spot is child lastIdx of path level lastL as ever).
     MT_HD int walk(int kind, int pos, int r, int c, int cand, int candLen, int L0 = 0, int rEnd = 0, int rMode = 0,
-                   int rSq = 0, int rOpset = -1, int rPm = 0) {
+                   int rSq = 0, int rOpset = -1, int rPm = 0, bool defer = false) {
         if (!(uValid && uRef == r && uCli == c)) { computeU(r, c, false); L0 = 0; }
         int B = root, L = 0, p = pos;
         if (L0 > 0) { B = uni(sc->pathB[L0]); L = L0; p = pos - uni(sc->pathOff[L0]); }
@@ -2223,6 +2285,13 @@ template <int RES, bool FULL = true> struct MtEngT {
                     if (pj > 0 && !(sm & MT_M_MARKER)) {
                         const int n = splitRow(s, pj, lf, j);
                         if (n < 0) return MT_W_FAIL;
+                        if (MT_INSERT_LEAF && kind == MT_WALK_SPLIT && defer) {
+                            // the half is written and owns its text; opInsert links it together with
+                            // the row it inserts (rows out of their block's children are still found
+                            // by compaction, which goes by the rows' parent field)
+                            pendR = n; lastIdx = j + 1;
+                            return MT_W_OK;
+                        }
                         insertAtPath(L, j + 1, n, 0);
                         if (FULL && drec) {                     // SPLIT, splitLeafSegment (mergeTree.ts:2243-2258)
                             const int ps = obsPosition(s);
@@ -3369,7 +3438,14 @@ template <int RES, bool FULL = true> struct MtEngT {
                         int markerId, const LaneArr<int>& pay) {
         // MergeTree.insertSegments (MT/mergeTree.ts:1974-2011)
         MT_PB(t0);
-        int w = walk(MT_WALK_SPLIT, pos, r, c, -1, 0);
+        // MT_INSERT_LEAF: a row split here leaves its right half unlinked, and the half goes into
+        // the block with the new row in one visit below.  The half before the new row in row
+        // order, the new row's text before it is linked: row ids and compaction as ever.  No
+        // block splits in between, so the second walk from the root (and its perspective set)
+        // is never needed.  Delta capture takes the two-visit path.
+        const bool pair = MT_INSERT_LEAF && !(FULL && drec != nullptr);
+        pendR = -1;
+        int w = walk(MT_WALK_SPLIT, pos, r, c, -1, 0, 0, 0, 0, 0, -1, 0, pair);
         MT_PE(MT_PH_SPLIT, t0);
         if (w == MT_W_OK) c_rows += 2;
         if (status) return;
@@ -3409,7 +3485,16 @@ template <int RES, bool FULL = true> struct MtEngT {
             wave_sync();
             MT_PB(t1);
             landB = -1;
-            if ((w == MT_W_OK || w == MT_W_NOCHANGE) && !lastSplit) {
+            if (pair) {
+                // A walk that failed found no place for pos under (r, c); the insert walk, by
+                // the same rule in the same tree, would find none either.
+                if (w == MT_W_OK || w == MT_W_NOCHANGE) {
+                    insertAtPath<true>(lastL, lastIdx, n, L, pendR, lastIdx + 1, lastIdx, lastIdx);   // the new row second
+                    if (pendR >= 0) { MT_EVR(6, lastSplit ? (1ull << 32) + 1 : 1); }
+                    uValid = false;
+                    w = MT_W_OK;
+                }
+            } else if ((w == MT_W_OK || w == MT_W_NOCHANGE) && !lastSplit) {
                 // The split walk (ensureIntervalBoundary) and the insert walk descend
                 // by the same rule; with no block split in between the insert walk
                 // would reach the same leaf slot: lastIdx (before the found row, at
@@ -3426,6 +3511,9 @@ template <int RES, bool FULL = true> struct MtEngT {
             const uint32_t m1 = winAddKnown(n, m0);
             if (sq > minSeq) addToLRUSetKnown(n, sq, landB, m1);
             if (FULL && drec) emitDelta(MT_DK_INSERT, obsPosition(n), L, n, uni(row(n).props), -1, -1);   // insertSegments callback
+        } else if (pendR >= 0) {                       // an empty insert: only the boundary it asked for
+            insertAtPath(lastL, lastIdx, pendR, 0);
+            if (lastSplit) uValid = false;
         }
         zamboni();
     }

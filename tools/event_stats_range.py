@@ -32,3 +32,12 @@ msgs = float(docs * c["ops"]); t = (raw - base).sum(axis=0).astype(float)
 names = ["range ops", "fused", "both boundaries in one leaf", "no room for the splits", "refused otherwise", "rows split by the fused step"]
 print(f"{cfg} docs={docs} res={res}, per message: " + "  ".join(f"{nm} {t[i]/msgs:.3f}" for i, nm in enumerate(names)))
 print("share of range ops: " + "  ".join(f"{nm} {100*t[i]/max(t[0],1):.1f}%" for i, nm in enumerate(names) if 0 < i < 5))
+# MT_LEAF_SPLIT: the "no room" range ops that rangeLeaf applies all the same (slot 7; slot 1 counts none of them).
+# MT_INSERT_LEAF (slot 6, low / high 32 bits): each paired insert saves one visit to its leaf block
+# (insertAtPath); one whose block of 7 splits under the half also saves the computeU and the root walk
+# that the two-visit path needs after that split (a block of 6 splits under the new row: nothing follows).
+pair = float((raw - base)[:, 6].astype(np.uint64).__and__(np.uint64(0xFFFFFFFF)).sum())
+psplit = float(((raw - base)[:, 6] >> np.uint64(32)).sum())
+print(f"range ops applied across a block split {t[7]/msgs:.4f} per message ({100*t[7]/max(t[0],1):.1f}% of range ops)")
+print(f"inserts per message: right half and new row linked together {pair/msgs:.4f}  of those splitting their block "
+      f"{psplit/msgs:.4f}")
