@@ -474,7 +474,7 @@ struct __attribute__((aligned(16), may_alias)) MtQ16a { uint32_t x, y, z, w; };
 #define MT_RANGE_LEAF 1               // opRange: a range inside one leaf block is applied in the start walk's visit
 #endif
 #ifndef MT_LEAF_SPLIT
-#define MT_LEAF_SPLIT 0               // rangeLeaf: also where the right halves split the leaf block (off: DESIGN.md §8)
+#define MT_LEAF_SPLIT 1               // rangeLeaf: also where the right halves split the leaf block
 #endif
 #ifndef MT_INSERT_LEAF
 #define MT_INSERT_LEAF 1              // opInsert: a split row's right half and the new row enter their leaf block together
@@ -2014,7 +2014,8 @@ template <int RES, bool FULL = true> struct MtEngT {
                 wave_for(8, [&](int i) MT_LAM { bk(B).c[i] = i < n1 ? own(nc, i) : -1; });
                 bk(B).n = n1; bk(B).len = h.len + delta;
                 // ancestors on the path: one lane per level (distinct blocks), one round trip
-                if (delta != 0) wave_for(L, [&](int l) MT_LAM { const int pb = sc->pathB[l]; bk(pb).len = bk(pb).len + delta; });
+                // (mt_opaque: &pathB[lane] is not kept from the kernel's entry, where it took a spill slot)
+                if (delta != 0) wave_for(L, [&](int l) MT_LAM { const int pb = sc->pathB[mt_opaque(l)]; bk(pb).len = bk(pb).len + delta; });
                 return;
             }
             lastSplit = true;
@@ -2196,7 +2197,7 @@ template <int RES, bool FULL = true> struct MtEngT {
         if (rem && room) {
             bk(B).len = h.len + obsDelta;
             if (L > 0 && obsDelta != 0) {                    // ancestors on the path: one lane per level
-                wave_for(L, [&](int l) MT_LAM { const int pb = sc->pathB[l]; bk(pb).len = bk(pb).len + obsDelta; });
+                wave_for(L, [&](int l) MT_LAM { const int pb = sc->pathB[mt_opaque(l)]; bk(pb).len = bk(pb).len + obsDelta; });   // as insertAtPath
                 wave_sync();
             }
         }
@@ -2908,7 +2909,8 @@ template <int RES, bool FULL = true> struct MtEngT {
                 MT_ZB(z6);
                 bk(p).scour = 0;
                 if (nh < h.n) {
-                    wave_for(8, [&](int j) MT_LAM { bk(p).c[j] = j < nh ? sc->hold[j] : -1; });
+                    // (mt_opaque: &hold[lane] is not kept from the kernel's entry, where it took a spill slot)
+                    wave_for(8, [&](int j) MT_LAM { bk(p).c[j] = j < nh ? sc->hold[mt_opaque(j)] : -1; });
                     bk(p).n = nh;
                     wave_sync();
                     // A scour keeps every block's observer length: unlinked rows were removed
@@ -3063,8 +3065,9 @@ template <int RES, bool FULL = true> struct MtEngT {
             wave_for(n, [&](int i) MT_LAM { if (own(keep, i)) { sc->hold[own(rk, i)] = own(kk, i); sc->holdLen[own(rk, i)] = own(vv, i); } });
             wave_sync();
             n = cntk;
-            kk = wave_map(n, [&](int i) MT_LAM { return sc->hold[i]; });
-            vv = wave_map(n, [&](int i) MT_LAM { return sc->holdLen[i]; });
+            // (mt_opaque: &hold[lane] and &holdLen[lane] are not kept from the kernel's entry in spill slots)
+            kk = wave_map(n, [&](int i) MT_LAM { return sc->hold[mt_opaque(i)]; });
+            vv = wave_map(n, [&](int i) MT_LAM { return sc->holdLen[mt_opaque(i)]; });
             wave_sync();
         }
         if (pm >= MT_PM_INCR && !S.p_vinfo) { status |= MT_DS_UNSUPPORTED; return old; }
@@ -3277,7 +3280,7 @@ template <int RES, bool FULL = true> struct MtEngT {
         }
         if (L0 > 0 && topD != 0) {                           // ancestors above the start block: one lane each
             const int dd = topD;
-            wave_for(L0, [&](int l) MT_LAM { const int pb = sc->pathB[l]; bk(pb).len = bk(pb).len + dd; });
+            wave_for(L0, [&](int l) MT_LAM { const int pb = sc->pathB[mt_opaque(l)]; bk(pb).len = bk(pb).len + dd; });   // as insertAtPath
             wave_sync();
         }
         uValid = false;
@@ -3457,9 +3460,13 @@ template <int RES, bool FULL = true> struct MtEngT {
             const bool nonl = !marker && plen <= MT_WAVE &&
                               wave_count(wave_map(plen, [&](int k) MT_LAM { return own(pay, k) == (int)'\n'; })) == 0;
             const uint32_t m0 = (uint32_t)c | (marker ? MT_M_MARKER : 0u) | (nonl ? MT_M_NONL : 0u);
-            row(n).len = L; row(n).seq = sq; row(n).rseq = MT_NOREM;
+            // (mt_opaque: the constant fields of the two 16-byte stores are made here; left to the
+            // compiler they live in two 4-register tuples carried, and spilled, around the replay loop)
+            const int norem = mt_opaque(MT_NOREM), zero = mt_opaque(0);
+            row(n).len = L; row(n).seq = sq; row(n).rseq = norem;
             row(n).meta = m0;
-            row(n).ovl = 0ull; row(n).parent = -1; row(n).rcl = 0u;
+            row(n).ovl = (unsigned long long)(uint32_t)zero | ((unsigned long long)(uint32_t)zero << 32);
+            row(n).parent = -1; row(n).rcl = (uint32_t)zero;
             row(n).mid = markerId >= 0 ? markerId + 1 : 0;
             if (markerId >= 0) {                       // mapIdToSegment before the walk (MT/mergeTree.ts:2218-2222)
                 if (markerId >= midCap) { status |= MT_DS_UNSUPPORTED; return; }
