@@ -1161,31 +1161,42 @@ int MT_FN(get_length)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t
 // written here from the text and the property-map chunks the kernel copied.
 // kind: MT_QK_LOCAL for position queries (a caller's ref_seq < 0 is the local view whatever its
 // value), else the tile-search kind every query of the call carries in `ref` (mt_query.h).
-static int mt_run_queries(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t* pos, const int32_t* ref,
-                          const int32_t* cli, std::vector<MtQueryOut>& res, int kind = MT_QK_LOCAL) {
-    res.assign(n, MtQueryOut{});
-    if (n == 0) return MT_OK;
+// The staging both query paths share: the queries sorted by document into q (ord[k]: the caller's
+// index of sorted query k), their groups uploaded with them.  ng: the groups.
+static int mt_stage_queries(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t* pos, const int32_t* ref,
+                            const int32_t* cli, int kind, std::vector<uint32_t>& ord, std::vector<MtQuery>& q, uint32_t& ng) {
     for (uint32_t i = 0; i < n; i++) if (docs[i] >= c->S.maxDocs) { c->err = "query document out of range"; return MT_E_INVALID; }
-    std::vector<uint32_t> ord(n);
+    ord.resize(n);
     for (uint32_t i = 0; i < n; i++) ord[i] = i;
     std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return docs[a] < docs[b]; });
-    std::vector<MtQuery> q(n);
+    q.resize(n);
     std::vector<uint32_t> grp;
     for (uint32_t k = 0; k < n; k++) {
         const uint32_t i = ord[k];
-        q[k].doc = docs[i]; q[k].pos = pos[i]; q[k].client = cli ? cli[i] : -1;
+        q[k].doc = docs[i]; q[k].pos = pos ? pos[i] : (int32_t)i; q[k].client = cli ? cli[i] : -1;
         q[k].ref = kind != MT_QK_LOCAL ? kind : ((ref && ref[i] >= 0) ? ref[i] : MT_QK_LOCAL);
         if (k == 0 || docs[i] != docs[ord[k - 1]]) grp.push_back(k);
     }
     grp.push_back(n);
-    const uint32_t ng = (uint32_t)grp.size() - 1;
+    ng = (uint32_t)grp.size() - 1;
     int rc;
     if ((rc = mtb_ensure(c, c->b_q, sizeof(MtQuery) * n))) return rc;
     if ((rc = mtb_ensure(c, c->b_qgrp, 4ull * (ng + 1)))) return rc;
-    if ((rc = mtb_ensure(c, c->b_qout, sizeof(MtQueryOut) * n))) return rc;
     if ((rc = mtb_sync(c))) return rc;
     mtb_h2d(c, c->b_q.p, q.data(), sizeof(MtQuery) * n);
     mtb_h2d(c, c->b_qgrp.p, grp.data(), 4ull * (ng + 1));
+    return MT_OK;
+}
+static int mt_run_queries(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t* pos, const int32_t* ref,
+                          const int32_t* cli, std::vector<MtQueryOut>& res, int kind = MT_QK_LOCAL) {
+    res.assign(n, MtQueryOut{});
+    if (n == 0) return MT_OK;
+    std::vector<uint32_t> ord;
+    std::vector<MtQuery> q;
+    uint32_t ng = 0;
+    int rc;
+    if ((rc = mt_stage_queries(c, n, docs, pos, ref, cli, kind, ord, q, ng))) return rc;
+    if ((rc = mtb_ensure(c, c->b_qout, sizeof(MtQueryOut) * n))) return rc;
     if ((rc = mtb_launch_query(c, (const MtQuery*)c->b_q.p, (const uint32_t*)c->b_qgrp.p, (MtQueryOut*)c->b_qout.p, ng))) return rc;
     if ((rc = mtb_sync(c))) return rc;
     std::vector<MtQueryOut> tmp(n);
@@ -1316,6 +1327,68 @@ int MT_FN(tile_index)(mt_ctx* c, uint32_t n, const uint32_t* docs, const uint32_
     *recs = c->tile_recs.data();
     *rec_off = c->tile_off.data();
     return MT_OK;
+}
+
+// Text ranges (mt_query.h): the records go up once per pass (the fill's carry the offsets the
+// counts gave), the text comes down once.  The query kernel's answer records are not used by the
+// text kinds, so none is allocated or downloaded.
+int MT_FN(get_text_range)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t* start, const int32_t* end,
+                          const int32_t* ref, const int32_t* cli, const uint16_t* placeholder, uint32_t placeholder_len,
+                          const uint16_t** arena, const uint64_t** off) {
+    if (!c || !arena || !off || (n && !docs) || (placeholder_len && !placeholder)) return MT_E_INVALID;
+    if (placeholder_len > MT_TEXT_PLACEHOLDER_MAX) { c->err = "text range: the placeholder is longer than MT_TEXT_PLACEHOLDER_MAX units"; return MT_E_INVALID; }
+    c->range_off.assign((size_t)n + 1, 0);
+    c->range_arena.clear();
+    *arena = c->range_arena.data(); *off = c->range_off.data();
+    if (n == 0) return MT_OK;
+    if (n > 0x7FFFFFFFu) { c->err = "text range: too many queries"; return MT_E_INVALID; }
+    std::vector<MtTextQ> x(n);
+    for (uint32_t i = 0; i < n; i++) {
+        x[i].start = start ? start[i] : 0; x[i].end = end ? end[i] : MT_POS_UNDEFINED;
+        x[i].ref = (ref && ref[i] >= 0) ? ref[i] : -1; x[i].client = cli ? cli[i] : -1;
+        x[i].at = 0; x[i].count = 0; x[i].filled = 0; x[i].pad = 0;
+    }
+    std::vector<uint32_t> ord;
+    std::vector<MtQuery> q;
+    uint32_t ng = 0;
+    int rc;
+    if ((rc = mt_stage_queries(c, n, docs, nullptr, nullptr, nullptr, MT_QK_TEXT_COUNT, ord, q, ng))) return rc;
+    if ((rc = mtb_ensure(c, c->b_xq, sizeof(MtTextQ) * n))) return rc;
+    mtb_h2d(c, c->b_xq.p, x.data(), sizeof(MtTextQ) * n);
+    c->S.x_q = (MtTextQ*)c->b_xq.p; c->S.x_nq = n; c->S.x_phlen = placeholder_len;
+    for (uint32_t k = 0; k < MT_TEXT_PLACEHOLDER_MAX / 2; k++) {
+        const uint32_t a = 2 * k < placeholder_len ? placeholder[2 * k] : 0u, b = 2 * k + 1 < placeholder_len ? placeholder[2 * k + 1] : 0u;
+        c->S.x_ph[k] = a | (b << 16);
+    }
+    c->S.x_out = nullptr; c->S.x_cap = 0;
+    auto done = [&](int r) { c->S.x_q = nullptr; c->S.x_nq = 0; c->S.x_out = nullptr; c->S.x_cap = 0; return r; };
+    if ((rc = mtb_launch_query(c, (const MtQuery*)c->b_q.p, (const uint32_t*)c->b_qgrp.p, (MtQueryOut*)c->b_qout.p, ng))) return done(rc);
+    if ((rc = mtb_sync(c))) return done(rc);
+    mtb_d2h(c, x.data(), c->b_xq.p, sizeof(MtTextQ) * n);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        x[i].at = total; c->range_off[i] = total;
+        total += x[i].count;
+        if (total > 0x80000000ull) { c->err = "text range: the answers hold more than 2^31 units; split the call"; return done(MT_E_INVALID); }
+    }
+    c->range_off[n] = total;
+    if (total) {
+        if ((rc = mtb_ensure(c, c->b_xout, 2ull * total))) return done(rc);
+        mtb_h2d(c, c->b_xq.p, x.data(), sizeof(MtTextQ) * n);
+        for (uint32_t k = 0; k < n; k++) q[k].ref = MT_QK_TEXT_FILL;
+        mtb_h2d(c, c->b_q.p, q.data(), sizeof(MtQuery) * n);
+        c->S.x_out = (uint16_t*)c->b_xout.p; c->S.x_cap = total;
+        if ((rc = mtb_launch_query(c, (const MtQuery*)c->b_q.p, (const uint32_t*)c->b_qgrp.p, (MtQueryOut*)c->b_qout.p, ng))) return done(rc);
+        if ((rc = mtb_sync(c))) return done(rc);
+        std::vector<MtTextQ> y(n);
+        mtb_d2h(c, y.data(), c->b_xq.p, sizeof(MtTextQ) * n);
+        for (uint32_t i = 0; i < n; i++)
+            if (y[i].filled != x[i].count) { c->err = "text range: the passes disagree"; return done(MT_E_INVALID); }
+        c->range_arena.resize((size_t)total);
+        mtb_d2h(c, c->range_arena.data(), c->b_xout.p, 2ull * total);
+    }
+    *arena = c->range_arena.data(); *off = c->range_off.data();
+    return done(MT_OK);
 }
 
 int MT_FN(resolve_remote_position)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t* pos, const int32_t* ref,

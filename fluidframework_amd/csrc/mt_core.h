@@ -315,6 +315,18 @@ struct MtState {                              // device pools, doc-major
     // index's record array (t_cap records)
     const uint8_t* t_match; uint32_t t_key, t_nvalues;
     mt_tile_rec* t_out; unsigned long long t_cap;
+    // text ranges (mt_query.h; set per call by mt_get_text_range): the call's query records
+    // (MtQuery::pos indexes them), the placeholder a marker stands for (x_phlen <= 16 UTF-16
+    // units, two a word) and the fill pass's output arena (x_cap units)
+    struct MtTextQ* x_q; uint32_t x_nq, x_phlen;
+    uint32_t x_ph[MT_TEXT_PLACEHOLDER_MAX / 2];
+    uint16_t* x_out; unsigned long long x_cap;
+};
+// One text-range query: the range and the view as the caller gave them, where the answer goes
+// in the arena, the units the count pass found and those the fill pass wrote.
+struct __attribute__((aligned(16))) MtTextQ {
+    int32_t start, end, ref, client;
+    unsigned long long at, count, filled, pad;
 };
 #define MT_VINFO_ID    0x3FFFFFFF
 #define MT_VINFO_NONE  0x3FFFFFFF

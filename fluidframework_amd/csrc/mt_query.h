@@ -5,10 +5,14 @@
 // and tile search (mt_find_tile, mt_tile_index) over a document-order scan of the rows:
 //   MergeTree.findTile                    MT/mergeTree.ts:1752-1778 (search :1780-1820,
 //                                         backwardSearch :1822-1866; the rule: include/mtgpu.h)
+// and text ranges under any view (mt_get_text_range) over the same scan:
+//   MergeTreeTextHelper.getText           MT/textSegment.ts:163-194 (gatherText :196-284, over
+//                                         mapRange -> nodeMap MT/mergeTree.ts:2927-2994)
 // Batched: the host groups the queries by document, one wave takes a document's queries
 // in order (the perspective's U set is reused while consecutive queries share it).  A
 // query reads the document and writes only the wave's U scratch of that document; a tile
-// query writes nothing of the document at all (its stack is the wave's LDS scratch).
+// query writes nothing of the document at all (its stack is the wave's LDS scratch), nor does
+// a text range in the local view.
 #pragma once
 #include "mt_core.h"
 
@@ -19,6 +23,10 @@
 #define MT_QK_TILE (-2)
 #define MT_QK_TILE_COUNT (-3)
 #define MT_QK_TILE_FILL (-4)
+// a text range (mt_get_text_range): pos is the query's record in MtState::x_q, which holds the
+// range and the view; the count pass and the fill pass of the same scan
+#define MT_QK_TEXT_COUNT (-5)
+#define MT_QK_TEXT_FILL (-6)
 #define MT_QT_PRECEDING 0x40000000
 struct __attribute__((aligned(16))) MtQuery { uint32_t doc; int32_t pos, ref, client; };   // ref < 0: local view / kind
 // One answer: the ABI record, where the found row's text sits in the text pool, and the
@@ -54,15 +62,16 @@ struct MtTileUnit {
     int vis, tvis;       // the unit's visible length, and that of its text rows
     int height;          // the unit block's height (0: the root alone)
 };
-enum { MT_TD_POS = 0, MT_TD_FIRST_VIS, MT_TD_LAST_VIS, MT_TD_FIRST, MT_TD_LAST };
+enum { MT_TD_POS = 0, MT_TD_FIRST_VIS, MT_TD_LAST_VIS, MT_TD_FIRST, MT_TD_LAST, MT_TD_PATH };
 
 template <class Eng> MT_HD bool mt_tile_blk_ok(const Eng& e, int b) { return b >= 0 && b < e.blkTop; }
 
 // Down from block B (observer start `base`) to a unit: at each level the child holding
 // observer position P (MT_TD_POS; P < the block's length), the first / last child of non-zero
-// observer length, or the first / last child.  False: no such child (or a broken tree).
+// observer length, the first / last child, or the child a containing() path names (MT_TD_PATH:
+// `depth` levels from the root, 3 bits each, root first).  False: no such child (or a broken tree).
 template <class Eng>
-MT_HD bool mt_tile_down(Eng& e, MtTileCursor& c, int B, int base, int P, int mode) {
+MT_HD bool mt_tile_down(Eng& e, MtTileCursor& c, int B, int base, int P, int mode, unsigned long long path = 0, int depth = 0) {
     for (;;) {
         if (!mt_tile_blk_ok(e, B)) { c.U = -1; return false; }
         if (uni(e.bk(B).height) <= 1) { c.U = B; c.base = base; return true; }
@@ -84,6 +93,8 @@ MT_HD bool mt_tile_down(Eng& e, MtTileCursor& c, int B, int base, int P, int mod
         } else if (mode == MT_TD_FIRST_VIS || mode == MT_TD_LAST_VIS) {
             const uint64_t m = wave_ballot(wave_map(n, [&](int k) MT_LAM { return own(lens, k) > 0; }));
             j = !m ? -1 : (mode == MT_TD_FIRST_VIS ? __builtin_ctzll(m) : 63 - __builtin_clzll(m));
+        } else if (mode == MT_TD_PATH) {
+            j = depth - 1 - c.lvl >= 0 ? (int)((path >> (3 * (depth - 1 - c.lvl))) & 7ull) : -1;
         } else j = mode == MT_TD_FIRST ? 0 : n - 1;
         if (j < 0 || j >= n) { c.U = -1; return false; }
         e.sc->pathB[c.lvl] = B; e.sc->pathJ[c.lvl] = j; e.sc->pathOff[c.lvl] = base;
@@ -125,27 +136,34 @@ MT_HD bool mt_tile_next(Eng& e, MtTileCursor& c, int dir, bool all) {
     c.U = -1;
     return false;
 }
-// Loads the cursor's unit: each lane its leaf block's child id and count, then the row's
-// first two quads (len seq rseq meta | toff props parent tcap), as scourLeaves does.
+// The row ids of the cursor's unit (-1: no row in that lane): each lane its leaf block's child
+// id and count, every block and row id checked against the document's tops.
 template <class Eng>
-MT_HD void mt_tile_unit(Eng& e, const MtTileCursor& c, MtTileUnit& u) {
+MT_HD LaneArr<int> mt_tile_unit_rows(Eng& e, const MtTileCursor& c, int& height, int& span) {
     BlkH h;
     const auto ch = e.blkLoad(c.U, h);
-    u.height = h.height;
+    height = h.height;
     const int U = c.U, hn = h.n < 0 ? 0 : (h.n > MT_MAXN ? MT_MAXN : h.n);
     const bool leafRoot = h.height == 0;
     const int nb = leafRoot ? 1 : hn;
     const auto blks = wave_map(8, [&](int j) MT_LAM { return leafRoot ? (j == 0 ? U : -1) : own(ch, j); });
-    const int span = 8 * nb;
+    span = 8 * nb;
     const auto bsel = wave_gather8(blks);
     const int btop = e.blkTop, rtop = e.rowTop;
-    u.row = wave_map(span, [&](int t) MT_LAM {
+    return wave_map(span, [&](int t) MT_LAM {
         const int b = own(bsel, t);
         const bool ok = (b >= 0) & (b < btop);
         const int bb = ok ? b : 0;
         const int g = e.bk(bb).c[t & 7];
         return (ok & ((t & 7) < e.bk(bb).n) & (g >= 0) & (g < rtop)) ? g : -1;
     });
+}
+// Loads the cursor's unit: the row ids, then the row's first two quads (len seq rseq meta |
+// toff props parent tcap), as scourLeaves does.
+template <class Eng>
+MT_HD void mt_tile_unit(Eng& e, const MtTileCursor& c, MtTileUnit& u) {
+    int span = 0;
+    u.row = mt_tile_unit_rows(e, c, u.height, span);
     const auto q0 = wave_map(span, [&](int t) MT_LAM {
         const int g = own(u.row, t);
         return g >= 0 ? ((const MtQ16a*)&e.row(g))[0] : MtQ16a{0u, 0u, 0u, 0u};
@@ -342,11 +360,149 @@ MT_HD int mt_tile_index_doc(Eng& e, const MtState& S, int lab, MtTileMemo& memo,
     }
 }
 
+/* ------------------------------------------------------------ text ranges -- */
+// getText(refSeq, clientId, placeholder, start, end) of one document (the rule: include/mtgpu.h)
+// as one document-order scan from the unit holding the range's start.  A unit's rows are lane
+// data: each row's length under the view (vis_rc, branch-free per lane), the
+// exclusive scan that places it in the view, its clip to the range, and a second scan over the
+// output lengths.  The fill then runs one lane per *output* unit in rounds of 64: the lane finds
+// its row by a binary search of the output scan (kept in the wave's scratch), so the stores are
+// contiguous and one long row costs what many short ones do.  out null: count only.  Returns
+// the answer's length; units go to out[0 .. length), as far as `room` reaches.
+template <class Eng>
+MT_HD unsigned long long mt_text_range_doc(Eng& e, const MtState& S, int start, int end, int ref, int qc, uint16_t* out,
+                                           unsigned long long room) {
+    if (!mt_tile_blk_ok(e, e.root)) return 0;
+    const int E = end == (int)0x80000000 ? 0x7FFFFFFF : end;       // undefined: the view's length
+    // S > E: substring swaps, and only a text row holding both ends strictly inside answers;
+    // it is the row holding E, so the scan enters there and ends with that unit
+    const bool swapped = start > E;
+    const int lo = swapped ? E : (start < 0 ? 0 : start), hi = swapped ? start : E;
+    if (swapped ? lo <= 0 : hi <= lo) return 0;
+    const bool local = ref < 0;
+    const int r = local ? 0x7FFFFFFF : ref, c = (local || qc < 0 || qc >= MT_NONCOLLAB) ? MT_NOBODY : qc;
+    const int plen = S.x_phlen > MT_TEXT_PLACEHOLDER_MAX ? MT_TEXT_PLACEHOLDER_MAX : (int)S.x_phlen;
+    static_assert(MT_TEXT_PLACEHOLDER_MAX == 16, "the placeholder is picked from eight words");
+    const int* phw = (const int*)S.x_ph;            // read by constant index only (pick8)
+    MtTileCursor cur; cur.U = -1; cur.lvl = 0; cur.base = 0;
+    int ubase = 0, s0 = -1, off0 = 0;
+    if (local) {
+        // the observer's lengths are the view's: subtrees of length 0 hold nothing
+        if (lo >= uni(e.bk(e.root).len)) return 0;
+        if (!mt_tile_down(e, cur, e.root, 0, lo, MT_TD_POS)) return 0;
+        ubase = cur.base;
+    } else {
+        // one descent under the view (it computes U once); the cursor is rebuilt from its path
+        int depth = 0;
+        unsigned long long path = 0;
+        s0 = e.containing(lo, r, c, off0, depth, path);
+        if (s0 < 0) return 0;
+        if (!mt_tile_down(e, cur, e.root, 0, 0, MT_TD_PATH, path, depth)) return 0;
+    }
+    unsigned long long done = 0;
+    const int ttop = e.textTop;
+    for (bool first = true;; first = false) {
+        int height = 0, span = 0;
+        const auto row = mt_tile_unit_rows(e, cur, height, span);
+        // len seq rseq meta | toff props parent tcap | ovl rcl mid (the third for a remote view only)
+        const auto q0 = wave_map(span, [&](int t) MT_LAM {
+            const int g = own(row, t);
+            return g >= 0 ? ((const MtQ16a*)&e.row(g))[0] : MtQ16a{0u, 0u, 0u, 0u};
+        });
+        const auto q1 = wave_map(span, [&](int t) MT_LAM {
+            const int g = own(row, t);
+            return g >= 0 ? ((const MtQ16a*)&e.row(g))[1] : MtQ16a{0u, 0u, 0u, 0u};
+        });
+        const auto q2 = wave_map(local ? 0 : span, [&](int t) MT_LAM {
+            const int g = own(row, t);
+            return g >= 0 ? ((const MtQ16a*)&e.row(g))[2] : MtQ16a{0u, 0u, 0u, 0u};
+        });
+        const auto vl = wave_map(span, [&](int t) MT_LAM {
+            const MtQ16a a = own(q0, t), x = own(q2, t);
+            const int g = own(row, t), l = (int)a.x;
+            const unsigned long long ovl = (unsigned long long)x.x | ((unsigned long long)x.y << 32);
+            const bool vis = local ? (a.w & MT_M_REMOVED) == 0 : vis_rc((int)a.y, a.w, (int)a.z, x.z, ovl, r, c, e.ovx, e.ovxN, g);
+            return ((g >= 0) & vis & (l > 0)) ? l : 0;
+        });
+        const auto pre = wave_excl_scan(vl);
+        const int vsum = wave_sum(vl);
+        if (first && !local) {                      // the unit's start under the view, from the row containing() found
+            const int s = s0;
+            const int t0 = wave_first(wave_map(span, [&](int t) MT_LAM { return own(row, t) == s; }));
+            if (t0 < 0) return 0;
+            ubase = lo - off0 - wave_at(pre, t0);
+        }
+        const int ub = ubase;
+        // output units per row: the clip of [p, p + l) to [lo, hi); a marker 0 or the placeholder
+        const auto olen = wave_map(span, [&](int t) MT_LAM {
+            const int p = ub + own(pre, t), l = own(vl, t);
+            const bool marker = (own(q0, t).w & MT_M_MARKER) != 0;
+            const int a = lo > p ? lo : p, b = hi < p + l ? hi : p + l;
+            const bool one = ((p < lo) & (hi < p + l) & !marker) != 0;
+            const int n = swapped ? (one ? hi - lo : 0) : (b > a ? b - a : 0);
+            return marker ? (n > 0 ? plen : 0) : n;
+        });
+        const auto opre = wave_excl_scan(olen);
+        const int T = wave_sum(olen);
+        if (out && T > 0) {
+            // the output scan (inclusive) and each row's first source unit (-1: the placeholder)
+            wave_for(MT_WAVE, [&](int t) MT_LAM {
+                const int p = ub + own(pre, t);
+                const bool marker = (own(q0, t).w & MT_M_MARKER) != 0;
+                e.sc->hold[t] = own(opre, t) + own(olen, t);
+                e.sc->holdLen[t] = marker ? -1 : (int)own(q1, t).x + ((lo > p ? lo : p) - p);
+            });
+            wave_sync();
+            for (int base = 0; base < T; base += MT_WAVE) {
+                const int m = (T - base) < MT_WAVE ? (T - base) : MT_WAVE;
+                const unsigned long long d0 = done + (unsigned long long)base;
+                wave_for(m, [&](int k) MT_LAM {
+                    const int j = base + k;
+                    int t = 0;                      // the first row whose inclusive end passes j
+                    for (int step = 32; step; step >>= 1) t += (e.sc->hold[t + step - 1] <= j) ? step : 0;
+                    const int before = e.sc->hold[t ? t - 1 : 0];
+                    const int kk = j - (t ? before : 0), sx = e.sc->holdLen[t];
+                    // the text index clamped to the live half's top; stores bounded by the record's room
+                    int ti = sx + kk;
+                    ti = ti >= ttop ? ttop - 1 : ti;
+                    ti = ti < 0 ? 0 : ti;
+                    const bool tx = ((sx >= 0) & (ttop > 0)) != 0;
+                    const uint32_t w = (uint32_t)pick8(phw, (kk >> 1) & 7);
+                    const uint16_t v = tx ? e.text[ti] : (uint16_t)((kk & 1) ? (w >> 16) : (w & 0xFFFFu));
+                    if (d0 + (unsigned long long)k < room) out[d0 + (unsigned long long)k] = v;
+                });
+            }
+            wave_sync();
+        }
+        done += (unsigned long long)T;
+        if (swapped) break;
+        ubase += vsum;
+        if (ubase >= hi) break;                     // the running view position reached E
+        if (!mt_tile_next(e, cur, 1, !local)) break;    // remote: a row the observer removed may be visible
+        if (local) ubase = cur.base;
+    }
+    return done;
+}
+
 template <class Eng>
 MT_HD void mt_query_run(Eng& e, const MtState& S, const MtQuery* q, uint32_t q0, uint32_t q1, MtQueryOut* out) {
     MtTileMemo memo; memo.lab = -1; memo.ps = -1; memo.res = false;
     for (uint32_t i = q0; i < q1; i++) {
         const int pos = uni(q[i].pos), ref = uni(q[i].ref), qc = uni(q[i].client);
+        if (ref <= MT_QK_TEXT_COUNT) {              // a text range: its record holds the query and takes the count
+            const bool fill = ref == MT_QK_TEXT_FILL;
+            if (!S.x_q || (uint32_t)pos >= S.x_nq) continue;
+            MtTextQ& x = S.x_q[(uint32_t)pos];
+            const unsigned long long at = uni64(x.at), cap = uni64(x.count);
+            unsigned long long room = (fill && S.x_out && at < S.x_cap) ? S.x_cap - at : 0ull;
+            room = room < cap ? room : cap;
+            const unsigned long long cnt = mt_text_range_doc(e, S, uni(x.start), uni(x.end), uni(x.ref), uni(x.client),
+                                                             room ? S.x_out + at : nullptr, room);
+            MtTextQ* xp = &x;
+            wave_for(1, [&](int) MT_LAM { if (fill) xp->filled = cnt; else xp->count = cnt; });
+            wave_sync();
+            continue;
+        }
         if (ref <= MT_QK_TILE) {                    // tile search: the local view, nothing written to the document
             const int lab = qc & (MT_QT_PRECEDING - 1);
             if (ref == MT_QK_TILE) {

@@ -133,6 +133,8 @@ def _bind(lib, prefix: str):
                                                 ctypes.POINTER(P)]),
         tile_index=f("tile_index", ctypes.c_int, [P, U32, P, P, ctypes.POINTER(MtTileLabels), ctypes.POINTER(P),
                                                   ctypes.POINTER(P)]),
+        get_text_range=f("get_text_range", ctypes.c_int, [P, U32, P, P, P, P, P, P, U32, ctypes.POINTER(P),
+                                                          ctypes.POINTER(P)]),
         set_doc_snapshot_chunk=f("set_doc_snapshot_chunk", ctypes.c_int, [P, U32, P, P]),
         reserve_staging=f("reserve_staging", ctypes.c_int, [P, ctypes.c_uint64]),
         docs_resize=f("docs_resize", ctypes.c_int, [P, U32, P, P]),
@@ -678,6 +680,32 @@ class Engine:
         raw = ctypes.string_at(arena, int(offs[-1]) * 2) if offs[-1] else b""
         return [raw[2 * offs[i]:2 * offs[i + 1]].decode("utf-16-le", "surrogatepass") for i in range(len(d))]
 
+    def get_text_range(self, docs, start=None, end=None, ref_seq=None, client=None, placeholder: str = "") -> list[str]:
+        """mt_get_text_range: MergeTreeTextHelper.getText(ref_seq[i], client[i], placeholder,
+        start[i], end[i]) (MT/textSegment.ts:163-194) of each query, gathered on the device.
+        start / end: None (0 / the view's length) or a sequence whose elements may be None /
+        POS_UNDEFINED for undefined; a scalar is broadcast.  ref_seq None or < 0: the local view.
+        start > end gives what JS substring's swap gives (include/mtgpu.h).  Raw ABI: client is
+        the engine's per-document client index, and "*" is an ordinary one-unit placeholder."""
+        d = _u32(docs)
+        n = len(d)
+
+        def arr(a):
+            if a is None:
+                return None
+            return _i32([POS_UNDEFINED if x is None else int(x) for x in np.broadcast_to(np.asarray(a, object), (n,))])
+        s, e = arr(start), arr(end)
+        r = None if ref_seq is None else _i32(np.broadcast_to(np.asarray(ref_seq), (n,)))
+        c = None if client is None else _i32(np.broadcast_to(np.asarray(client), (n,)))
+        ph = np.frombuffer(placeholder.encode("utf-16-le", "surrogatepass"), np.uint16)
+        arena, off = ctypes.c_void_p(), ctypes.c_void_p()
+        ptr = lambda a: a.ctypes.data if a is not None and len(a) else None  # noqa: E731
+        self._check(self.fn["get_text_range"](self.h, n, ptr(d), ptr(s), ptr(e), ptr(r), ptr(c), ptr(ph), len(ph),
+                                              ctypes.byref(arena), ctypes.byref(off)), "mt_get_text_range")
+        offs = np.ctypeslib.as_array(ctypes.cast(off, ctypes.POINTER(ctypes.c_uint64)), (n + 1,)).copy()
+        raw = ctypes.string_at(arena, int(offs[-1]) * 2) if offs[-1] else b""
+        return [raw[2 * offs[i]:2 * offs[i + 1]].decode("utf-16-le", "surrogatepass") for i in range(n)]
+
     def dump(self, doc: int) -> np.ndarray:
         rows, n = ctypes.c_void_p(), ctypes.c_uint32()
         self._check(self.fn["dump_segments"](self.h, doc, ctypes.byref(rows), ctypes.byref(n)), "mt_dump_segments")
@@ -761,6 +789,37 @@ class Segment:
         return self._json
 
 
+def check_placeholder(placeholder: str) -> str:
+    """The placeholders the hosts take: "*" stands for "\\n" + marker.toString() in the reference
+    (textSegment.ts:265-267), which is not built (getTextRangeWithMarkers)."""
+    if placeholder == "*":
+        raise MergeTreeError('placeholder "*" (the markers\' toString form, getTextRangeWithMarkers) is not '
+                             "reproduced: DESIGN.md §7")
+    if len(placeholder.encode("utf-16-le", "surrogatepass")) // 2 > 16:
+        raise MergeTreeError("placeholder longer than 16 UTF-16 units (MT_TEXT_PLACEHOLDER_MAX)")
+    return placeholder
+
+
+class TextHelper:
+    """MergeTreeTextHelper (MT/textSegment.ts:163-194) of one MergeTreeClient."""
+
+    def __init__(self, client: "MergeTreeClient"):
+        self.client = client
+
+    def getText(self, refSeq: int, clientId: int, placeholder: str = "", start=None, end=None) -> str:
+        """getText(refSeq, clientId, placeholder, start, end): clientId is the Client's short id,
+        0 the local client, whose view is every sequenced op whatever refSeq is (as _query)."""
+        c = self.client
+        c.group.flush()
+        c._raise_status()
+        check_placeholder(placeholder)
+        if clientId is None or clientId == 0:
+            ref, cli = -1, -1
+        else:
+            ref, cli = int(refSeq), int(clientId) - 1
+        return c.engine.get_text_range([c.doc_id], [start], [end], [ref], [cli], placeholder)[0]
+
+
 class MergeTreeClient:
     """Drop-in subset of merge-tree ``Client`` (MT/client.ts:44) for a passive observer.
 
@@ -809,10 +868,18 @@ class MergeTreeClient:
         self._raise_status()
         return int(self.engine.get_length([self.doc_id], [0x7FFFFFFF], [-1])[0])
 
-    def getText(self) -> str:
+    def getText(self, start=None, end=None) -> str:
+        """The observer's text; with start / end, SharedString.getText(start, end)
+        (sequence/src/sharedString.ts:211-214) through mt_get_text_range."""
         self.group.flush()
         self._raise_status()
-        return self.engine.get_text([self.doc_id])[0]
+        if start is None and end is None:
+            return self.engine.get_text([self.doc_id])[0]
+        return self.engine.get_text_range([self.doc_id], [start], [end])[0]
+
+    def createTextHelper(self) -> "TextHelper":
+        """Client.createTextHelper (client.ts): MergeTreeTextHelper over this document."""
+        return TextHelper(self)
 
     def snapshot(self, catchUpMsgs: list | None = None, min_seq: int | None = None, seq: int | None = None) -> dict:
         """Client.snapshot (client.ts:923-956) as an ITree.  options

@@ -312,6 +312,25 @@ class Engine {
             Int32Array.from(seq));
     }
     getText(docs) { return addon.getText(this.h, Uint32Array.from(docs)); }
+    /**
+     * mt_get_text_range: MergeTreeTextHelper.getText(refSeq[i], client[i], placeholder, start[i],
+     * end[i]) (MT/textSegment.ts:163-194) of each query, gathered on the device.  start / end:
+     * undefined for all-undefined, or arrays whose elements may be undefined (start: 0, end: the
+     * view's length); refSeq undefined or < 0: the local view.  A number that is not an integer
+     * is a TypeError.  Raw ABI: client is the engine's per-document client index, and "*" is an
+     * ordinary one-unit placeholder.
+     */
+    getTextRange(docs, start, end, refSeq, client, placeholder = "") {
+        const n = docs.length;
+        const arr = (a, undef) => Int32Array.from({ length: n }, (_, i) => {
+            const v = a === undefined ? undefined : a[i];
+            if (v === undefined) return undef;
+            if (typeof v !== "number" || !Number.isInteger(v)) throw new TypeError(`getTextRange: ${String(v)} is not an integer`);
+            return Math.max(-(2 ** 31) + 1, Math.min(2 ** 31 - 1, v));
+        });
+        return addon.getTextRange(this.h, Uint32Array.from(docs), arr(start, -(2 ** 31)), arr(end, -(2 ** 31)), arr(refSeq, -1),
+            arr(client, -1), String(placeholder));
+    }
     /** Record the delta / maintenance callbacks of later batches (mt_delta_capture; 0: off). */
     deltaCapture(capacity) { addon.deltaCapture(this.h, capacity); }
     /** The last batch's records: Int32Array, 8 per record (op, kind, pos, len, seg, a, b, pad). */
@@ -414,10 +433,34 @@ class MergeTreeClient {
         this.checkStatus();
         return this.group.engine.getLength([this.docId], [0x7FFFFFFF], [-1])[0];
     }
-    getText() {
+    /** The observer's text; with start / end, SharedString.getText(start, end) (sharedString.ts:211-214). */
+    getText(start, end) {
         this.group.flush();
         this.checkStatus();
-        return this.group.engine.getText([this.docId])[0];
+        if (start === undefined && end === undefined) return this.group.engine.getText([this.docId])[0];
+        return this.group.engine.getTextRange([this.docId], [start], [end])[0];
+    }
+    /**
+     * Client.createTextHelper: MergeTreeTextHelper.getText(refSeq, clientId, placeholder, start,
+     * end) (MT/textSegment.ts:163-194).  clientId is the short id, 0 the local client, whose view
+     * is every sequenced op whatever refSeq is.  The placeholder "*" ("\n" + marker.toString()
+     * in the reference, textSegment.ts:265-267) is refused: DESIGN.md §7.
+     */
+    createTextHelper() {
+        const client = this;
+        return {
+            getText(refSeq, clientId, placeholder = "", start, end) {
+                client.group.flush();
+                client.checkStatus();
+                if (placeholder === "*") {
+                    throw new Error("placeholder \"*\" (the markers' toString form, getTextRangeWithMarkers) is not reproduced: DESIGN.md §7");
+                }
+                if (placeholder.length > 16) throw new Error("placeholder longer than 16 UTF-16 units (MT_TEXT_PLACEHOLDER_MAX)");
+                const local = clientId === undefined || clientId === 0;
+                return client.group.engine.getTextRange([client.docId], [start], [end], [local ? -1 : refSeq],
+                    [local ? -1 : clientId - 1], placeholder)[0];
+            },
+        };
     }
     // Short client ids (client.ts:658-670): the local client 0, remote clients in first-seen order.
     getOrAddShortClientId(longClientId) {
@@ -747,7 +790,14 @@ class SequenceChannel {
             this.processCore(m, false);
         }
     }
-    getText() { return this.client.getText(); }
+    // SharedString's text reads (sequence/src/sharedString.ts:211-225): the collab window's
+    // (currentSeq, clientId) is the local view
+    getText(start, end) { return this.client.getText(start, end); }
+    getTextWithPlaceholders() { return this.client.createTextHelper().getText(this.client.currentSeq, 0, " "); }
+    getTextRangeWithPlaceholders(start, end) { return this.client.createTextHelper().getText(this.client.currentSeq, 0, " ", start, end); }
+    getTextRangeWithMarkers() {
+        throw new Error("getTextRangeWithMarkers (placeholder \"*\": \"\\n\" + marker.toString(), textSegment.ts:265-267) is not reproduced: DESIGN.md §7");
+    }
 }
 
 module.exports = { addon, Engine, ClientGroup, MergeTreeClient, BatchBuilder, PropTable, ClientNames, statusNames,

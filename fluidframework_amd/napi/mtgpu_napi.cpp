@@ -632,6 +632,35 @@ napi_value GetText(napi_env env, napi_callback_info info) {
     return out;
 }
 
+// getTextRange(ctx, docs, start: Int32Array, end: Int32Array, refSeq: Int32Array, client:
+// Int32Array, placeholder: string) -> [string] (mt_get_text_range; INT32_MIN in start / end is
+// undefined, refSeq < 0 the local view; the strings hold the UTF-16 code units as-is)
+napi_value GetTextRange(napi_env env, napi_callback_info info) {
+    napi_value argv[7];
+    if (!get_args(env, info, 7, argv)) return nullptr;
+    mt_ctx* c = get_ctx(env, argv[0]); if (!c) return nullptr;
+    const uint32_t* docs; const int32_t *st, *en, *ref, *cli; size_t n, n1, n2, n3, n4;
+    if (!typed(env, argv[1], napi_uint32_array, &docs, &n) || !typed(env, argv[2], napi_int32_array, &st, &n1) ||
+        !typed(env, argv[3], napi_int32_array, &en, &n2) || !typed(env, argv[4], napi_int32_array, &ref, &n3) ||
+        !typed(env, argv[5], napi_int32_array, &cli, &n4)) return nullptr;
+    if (n1 < n || n2 < n || n3 < n || n4 < n) { napi_throw_range_error(env, nullptr, "start/end/refSeq/client shorter than docs"); return nullptr; }
+    char16_t ph[MT_TEXT_PLACEHOLDER_MAX + 2]; size_t nph = 0;
+    if (napi_get_value_string_utf16(env, argv[6], ph, MT_TEXT_PLACEHOLDER_MAX + 2, &nph) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "placeholder is not a string"); return nullptr;
+    }
+    const uint16_t* arena = nullptr; const uint64_t* off = nullptr;
+    int rc = mt_get_text_range(c, (uint32_t)n, docs, st, en, ref, cli, (const uint16_t*)ph, (uint32_t)nph, &arena, &off);
+    if (rc) return throw_rc(env, c, rc, "mt_get_text_range");
+    napi_value out;
+    NAPI_OK(napi_create_array_with_length(env, n, &out));
+    for (size_t i = 0; i < n; i++) {
+        napi_value s;
+        napi_create_string_utf16(env, (const char16_t*)(arena + off[i]), (size_t)(off[i + 1] - off[i]), &s);
+        napi_set_element(env, out, (uint32_t)i, s);
+    }
+    return out;
+}
+
 // deltaCapture(ctx, capacity): record the delta / maintenance callbacks of later batches
 napi_value DeltaCapture(napi_env env, napi_callback_info info) {
     napi_value argv[2];
@@ -819,6 +848,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"growStats", nullptr, GrowStats, nullptr, nullptr, nullptr, kQuiet, nullptr},
         {"findTile", nullptr, FindTile, nullptr, nullptr, nullptr, kQuiet, nullptr},
         {"tileIndex", nullptr, TileIndex, nullptr, nullptr, nullptr, kQuiet, nullptr},
+        {"getTextRange", nullptr, GetTextRange, nullptr, nullptr, nullptr, kQuiet, nullptr},
     };
     napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
     return exports;

@@ -242,5 +242,17 @@ class SequenceDoc:
             self.process(m)
             self.client.current_seq = int(m["sequenceNumber"])
 
-    def getText(self) -> str:
-        return self.client.getText()
+    # SharedString's text reads (sequence/src/sharedString.ts:211-225): the collab window's
+    # (currentSeq, clientId) is the local view
+    def getText(self, start=None, end=None) -> str:
+        return self.client.getText(start, end)
+
+    def getTextWithPlaceholders(self) -> str:
+        return self.client.createTextHelper().getText(self.client.current_seq, 0, " ")
+
+    def getTextRangeWithPlaceholders(self, start, end) -> str:
+        return self.client.createTextHelper().getText(self.client.current_seq, 0, " ", start, end)
+
+    def getTextRangeWithMarkers(self, start, end) -> str:
+        raise NotImplementedError('getTextRangeWithMarkers (placeholder "*": "\\n" + marker.toString(), '
+                                  "textSegment.ts:265-267) is not reproduced: DESIGN.md §7")

@@ -640,6 +640,53 @@ typedef struct mt_tile_rec { int32_t pos, text_pos, row, prop_set, ref_type, mar
 int  mt_tile_index(mt_ctx* ctx, uint32_t n, const uint32_t* doc_ids, const uint32_t* label,
                    const mt_tile_labels* labels, const mt_tile_rec** recs, const uint64_t** rec_off);
 
+/*
+ * Ranges of text under any view, gathered on the device.
+ *   MergeTreeTextHelper.getText(refSeq, clientId, placeholder = "", start?, end?)
+ *                              MT/textSegment.ts:163-194 (gatherText :196-284)
+ *   mapRange -> nodeMap        MT/mergeTree.ts:2927-2994 (the visit test :2964)
+ *   nodeLength                 MT/mergeTree.ts:1652-1692 (the local client :1653-1659)
+ *   SharedString.getText(start, end), getTextWithPlaceholders(),
+ *   getTextRangeWithPlaceholders(start, end)   sequence/src/sharedString.ts:211-225
+ * The view is (ref_seq[i], client[i]) as mt_get_containing_segment takes it: ref_seq < 0, or
+ * ref_seq / client NULL, is the local view (every sequenced op applied, whatever refSeq is).
+ * Number the document's rows in order; l_i is row i's length under the view, p_i the sum of
+ * the l before it, L the sum of all.  S = start[i] (undefined: 0), E = end[i] (undefined: L).
+ * nodeMap visits row i when E - p_i > 0 && l_i > 0 && S - p_i < l_i (:2964).  A visited text
+ * row gives, with s = S - p_i and e = E - p_i: its whole text when s <= 0 and e >= l_i, else
+ * text.substring(max(s, 0)) when e >= l_i, else text.substring(max(s, 0), e)
+ * (textSegment.ts:251-262).  A visited marker gives the placeholder once (its length is 1),
+ * whole, whatever S and E are, and nothing when the placeholder is empty (:264-272).  So:
+ *   S <= E:  units [max(S, 0), min(E, L)) of the view's sequence, each marker in the range
+ *            replaced by the placeholder.  A negative S acts as 0; E <= 0 or S >= L gives "".
+ *   S > E:   JS substring swaps its arguments, and at most one row can be visited: a visible
+ *            text row with p_i < E and S < p_i + l_i.  The answer is that row's units
+ *            [E - p_i, S - p_i), else "".  This depends on how the text is segmented; it is
+ *            the reference's behaviour and is reproduced from the rows as they are.
+ *   Units are UTF-16 code units: a range may cut a surrogate pair, as substring does.
+ * Not reproduced: the placeholder "*", which in the reference stands for "\n" +
+ * marker.toString() (textSegment.ts:265-267, Marker.toString mergeTree.ts:717-790), host
+ * formatting of ids, labels and properties.  Here "*" has no special meaning: it is a
+ * one-unit placeholder like any other, and the hosts refuse it.  getTextAndMarkers is not
+ * provided.  The rule was derived by reading the reference, which could not be executed.
+ *
+ * Query i is answered by units [off[i], off[i+1]) of a library-owned arena of its own (valid
+ * until the next mt_get_text_range; mt_get_text's arena is not touched).  Queries may repeat a
+ * document and come in any order; one document's queries run in order in one wave.  start /
+ * end NULL: all 0 / all undefined; an element MT_POS_UNDEFINED: undefined.  The placeholder
+ * has at most MT_TEXT_PLACEHOLDER_MAX units (more: MT_E_INVALID).  An answer set above 2^31
+ * units in one call is MT_E_INVALID: split the call.  Nothing of a document is modified: a
+ * remote view writes only the wave's perspective scratch, as position queries do, a local
+ * view nothing.  Documents whose status word is set are read as they stand.  Two device passes
+ * over the same scan: count, then fill.
+ */
+#define MT_TEXT_PLACEHOLDER_MAX 16
+int  mt_get_text_range(mt_ctx* ctx, uint32_t n, const uint32_t* doc_ids,
+                       const int32_t* start, const int32_t* end,
+                       const int32_t* ref_seq, const int32_t* client,
+                       const uint16_t* placeholder, uint32_t placeholder_len,
+                       const uint16_t** arena, const uint64_t** off);
+
 /* Client long-id strings (JSON literals) by per-document client index; used for
  * the snapshot's "client"/"removedClient" fields (snapshotV1.ts:229, :237). */
 int  mt_set_client_names(mt_ctx* ctx, uint32_t n, const char* const* client_json);
