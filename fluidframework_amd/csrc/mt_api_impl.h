@@ -1391,6 +1391,141 @@ int MT_FN(get_text_range)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int
     return done(MT_OK);
 }
 
+// Segment walks (mt_query.h): as text ranges, the records go up once per pass and the fill's carry
+// the offsets the counts gave; the walk's records and text come down once.  Then the distinct
+// (document, prop_set) pairs the records name are fetched by one more launch of the query kernel
+// (MT_QK_PSET copies a map's chunks, packed, into a buffer the call's MtWalkCall names) and written out
+// once each.
+int MT_FN(walk_segments)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t* start, const int32_t* end,
+                         const int32_t* ref, const int32_t* cli, uint32_t flags, const mt_walk_rec** recs, const uint64_t** rec_off,
+                         const uint16_t** text_arena, const mt_walk_maps** maps) {
+    if (!c || !recs || !rec_off || (n && !docs)) return MT_E_INVALID;
+    if (flags & ~MT_WALK_TEXT) { c->err = "walk: unknown flags"; return MT_E_INVALID; }
+    const bool text = (flags & MT_WALK_TEXT) && text_arena;
+    c->walk_off.assign((size_t)n + 1, 0);
+    c->walk_recs.clear(); c->walk_arena.clear();
+    c->walk_map_doc.clear(); c->walk_map_ps.clear(); c->walk_map_key.clear(); c->walk_map_val.clear(); c->walk_map_json.clear();
+    c->walk_map_koff.assign(1, 0); c->walk_map_joff.assign(1, 0);
+    auto give = [&]() {
+        *recs = c->walk_recs.data(); *rec_off = c->walk_off.data();
+        if (text_arena) *text_arena = c->walk_arena.data();
+        c->walk_maps.n = (uint32_t)c->walk_map_doc.size();
+        c->walk_maps.doc = c->walk_map_doc.data(); c->walk_maps.prop_set = c->walk_map_ps.data();
+        c->walk_maps.key_off = c->walk_map_koff.data(); c->walk_maps.key = c->walk_map_key.data();
+        c->walk_maps.value = c->walk_map_val.data(); c->walk_maps.json_off = c->walk_map_joff.data();
+        c->walk_maps.json = c->walk_map_json.data();
+        if (maps) *maps = &c->walk_maps;
+    };
+    give();
+    if (n == 0) return MT_OK;
+    if (n > 0x7FFFFFFFu) { c->err = "walk: too many queries"; return MT_E_INVALID; }
+    std::vector<MtWalkQ> x(n);
+    for (uint32_t i = 0; i < n; i++) {
+        MtWalkQ& w = x[i];
+        w = MtWalkQ{};
+        w.start = start ? start[i] : 0; w.end = end ? end[i] : MT_POS_UNDEFINED;
+        w.ref = (ref && ref[i] >= 0) ? ref[i] : -1; w.client = cli ? cli[i] : -1;
+        for (const int32_t v : {w.start, w.end})
+            if (v != MT_POS_UNDEFINED && (v < -(1 << 30) || v > (1 << 30))) { c->err = "walk: start / end outside [-2^30, 2^30]"; return MT_E_INVALID; }
+    }
+    std::vector<uint32_t> ord;
+    std::vector<MtQuery> q;
+    uint32_t ng = 0;
+    int rc;
+    if ((rc = mt_stage_queries(c, n, docs, nullptr, nullptr, nullptr, MT_QK_WALK_COUNT, ord, q, ng))) return rc;
+    if ((rc = mtb_ensure(c, c->b_wq, sizeof(MtWalkQ) * n))) return rc;
+    mtb_h2d(c, c->b_wq.p, x.data(), sizeof(MtWalkQ) * n);
+    // the call's state lives in device memory, reached through x_walk (mt_core.h: MtState does not grow)
+    if ((rc = mtb_ensure(c, c->b_wcall, sizeof(MtWalkCall)))) return rc;
+    MtWalkCall call{};
+    call.q = (MtWalkQ*)c->b_wq.p; call.nq = n; call.flags = text ? MT_WALK_TEXT : 0u;
+    mtb_h2d(c, c->b_wcall.p, &call, sizeof call);
+    c->S.x_walk = (const MtWalkCall*)c->b_wcall.p; c->S.x_nq = 0; c->S.x_out = nullptr; c->S.x_cap = 0;
+    auto done = [&](int r) { c->S.x_q = nullptr; c->S.x_nq = 0; c->S.x_out = nullptr; c->S.x_cap = 0; return r; };
+    if ((rc = mtb_launch_query(c, (const MtQuery*)c->b_q.p, (const uint32_t*)c->b_qgrp.p, (MtQueryOut*)c->b_qout.p, ng))) return done(rc);
+    if ((rc = mtb_sync(c))) return done(rc);
+    mtb_d2h(c, x.data(), c->b_wq.p, sizeof(MtWalkQ) * n);
+    uint64_t total = 0, ttotal = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        x[i].at = total; x[i].tat = ttotal; c->walk_off[i] = total;
+        total += x[i].count; ttotal += x[i].tcount;
+        if (total > 0x80000000ull || ttotal > 0x80000000ull) {
+            c->walk_off.assign((size_t)n + 1, 0);
+            c->err = "walk: the answers hold more than 2^31 records or text units; split the call";
+            return done(MT_E_INVALID);
+        }
+    }
+    c->walk_off[n] = total;
+    if (!total) return done(MT_OK);
+    if ((rc = mtb_ensure(c, c->b_wout, sizeof(mt_walk_rec) * total))) return done(rc);
+    if (ttotal && (rc = mtb_ensure(c, c->b_wtext, 2ull * ttotal))) return done(rc);
+    mtb_h2d(c, c->b_wq.p, x.data(), sizeof(MtWalkQ) * n);
+    for (uint32_t k = 0; k < n; k++) q[k].ref = MT_QK_WALK_FILL;
+    mtb_h2d(c, c->b_q.p, q.data(), sizeof(MtQuery) * n);
+    call.out = (mt_walk_rec*)c->b_wout.p; call.cap = total;
+    mtb_h2d(c, c->b_wcall.p, &call, sizeof call);
+    if (ttotal) { c->S.x_out = (uint16_t*)c->b_wtext.p; c->S.x_cap = ttotal; }
+    auto fail = [&](int r) { c->walk_off.assign((size_t)n + 1, 0); return done(r); };
+    if ((rc = mtb_launch_query(c, (const MtQuery*)c->b_q.p, (const uint32_t*)c->b_qgrp.p, (MtQueryOut*)c->b_qout.p, ng))) return fail(rc);
+    if ((rc = mtb_sync(c))) return fail(rc);
+    std::vector<MtWalkQ> y(n);
+    mtb_d2h(c, y.data(), c->b_wq.p, sizeof(MtWalkQ) * n);
+    for (uint32_t i = 0; i < n; i++)
+        if (y[i].filled != x[i].count || y[i].tfilled != x[i].tcount) { c->err = "walk: the passes disagree"; return fail(MT_E_INVALID); }
+    c->walk_recs.resize((size_t)total);
+    mtb_d2h(c, c->walk_recs.data(), c->b_wout.p, sizeof(mt_walk_rec) * total);
+    c->walk_arena.resize((size_t)ttotal);
+    if (ttotal) mtb_d2h(c, c->walk_arena.data(), c->b_wtext.p, 2ull * ttotal);
+    done(MT_OK);
+    // the distinct maps, in the order the records first name them; the fill left each map's key
+    // count in the record's `map`, which places the maps' chunks
+    std::unordered_map<uint64_t, int32_t> seen;
+    std::vector<int32_t> mpos, mat, mkeys;
+    uint64_t chunks = 0;
+    for (uint32_t i = 0; i < n; i++)
+        for (uint64_t k = c->walk_off[i]; k < c->walk_off[i + 1]; k++) {
+            mt_walk_rec& w = c->walk_recs[(size_t)k];
+            if (!maps || w.prop_set < 0) { w.map = -1; continue; }
+            const uint64_t key = ((uint64_t)docs[i] << 32) | (uint32_t)w.prop_set;
+            auto it = seen.find(key);
+            if (it == seen.end()) {
+                it = seen.emplace(key, (int32_t)c->walk_map_doc.size()).first;
+                const uint32_t nk = w.map < 0 ? 0u : ((uint32_t)w.map > MT_PKEYS ? MT_PKEYS : (uint32_t)w.map);
+                c->walk_map_doc.push_back(docs[i]); c->walk_map_ps.push_back(w.prop_set);
+                mpos.push_back(w.prop_set); mat.push_back((int32_t)chunks); mkeys.push_back((int32_t)nk);
+                chunks += nk > MT_PSK ? (nk + MT_PSK - 1) / MT_PSK : 1;
+                if (chunks > 0x7FFFFFFFull) { c->err = "walk: the distinct maps hold more than 2^31 chunks; split the call"; return fail(MT_E_INVALID); }
+            }
+            w.map = it->second;
+        }
+    if (!c->walk_map_doc.empty()) {
+        const uint32_t m = (uint32_t)c->walk_map_doc.size();
+        if ((rc = mt_stage_queries(c, m, c->walk_map_doc.data(), mpos.data(), nullptr, mat.data(), MT_QK_PSET, ord, q, ng))) return fail(rc);
+        if ((rc = mtb_ensure(c, c->b_wmaps, sizeof(MtPSet) * chunks))) return fail(rc);
+        call.out = nullptr; call.cap = 0; call.maps = (MtPSet*)c->b_wmaps.p; call.mcap = chunks;
+        mtb_h2d(c, c->b_wcall.p, &call, sizeof call);
+        c->S.x_walk = (const MtWalkCall*)c->b_wcall.p;
+        rc = mtb_launch_query(c, (const MtQuery*)c->b_q.p, (const uint32_t*)c->b_qgrp.p, (MtQueryOut*)c->b_qout.p, ng);
+        if (!rc) rc = mtb_sync(c);
+        c->S.x_q = nullptr;
+        if (rc) return fail(rc);
+        std::vector<MtPSet> got((size_t)chunks);
+        mtb_d2h(c, got.data(), c->b_wmaps.p, sizeof(MtPSet) * chunks);
+        c->walk_map_key.reserve((size_t)chunks * MT_PSK); c->walk_map_val.reserve((size_t)chunks * MT_PSK);
+        for (uint32_t k = 0; k < m; k++) {
+            const MtPSet* p = got.data() + mat[k];
+            const uint32_t nk = (uint32_t)mkeys[k];
+            if (p[0].n != mkeys[k]) { c->err = "walk: the passes disagree on a property map"; return fail(MT_E_INVALID); }
+            for (uint32_t j = 0; j < nk; j++) { c->walk_map_key.push_back(p[j >> 4].key[j & 15]); c->walk_map_val.push_back(p[j >> 4].val[j & 15]); }
+            c->walk_map_koff.push_back(c->walk_map_key.size());
+            mtsnap::props_json(c->walk_map_json, p, c->names);
+            c->walk_map_joff.push_back(c->walk_map_json.size());
+        }
+    }
+    give();
+    return MT_OK;
+}
+
 int MT_FN(resolve_remote_position)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t* pos, const int32_t* ref,
                                    const int32_t* cli, int32_t* out) {
     if (!c || (n && (!docs || !pos || !out))) return MT_E_INVALID;

@@ -44,14 +44,16 @@ struct mt_ctx {
            b_ld_meta, b_ld_seg, b_ld_pay, b_ld_plan, b_ld_poff, b_dtext, b_resume, b_start,
            b_q, b_qgrp, b_qout, b_qat, b_qlen, b_qoff, b_qtext,   // position queries (mt_get_containing_segment)
            b_tmatch, b_tout,                                      // tile search: the labels' match arrays, the index's records
-           b_xq, b_xout;                                          // text ranges: the query records, the fill pass's arena
+           b_xq, b_xout,                                          // text ranges: the query records, the fill pass's arena
+           b_wcall, b_wq, b_wout, b_wtext, b_wmaps;                       // segment walks: the call, its query records, the fill pass's records and text, the maps' chunks
     DevBuf b_runs, b_batch;
     // Every device buffer above, for mt_destroy (one list beside the declarations).
     std::vector<DevBuf*> dev_bufs() {
         return {&b_stage, &b_pack_docs, &b_pack_sz, &b_pack_off, &b_gencl, &b_cursor, &b_doc, &b_off, &b_rec, &b_pay, &b_pbase,
                 &b_rel, &b_drec, &b_dcount, &b_pset_off, &b_pkey, &b_pval, &b_pfalsy, &b_pclass, &b_pkind, &b_tmp0, &b_tmp1,
                 &b_tmp2, &b_tmp3, &b_ld_meta, &b_ld_seg, &b_ld_pay, &b_ld_plan, &b_ld_poff, &b_dtext, &b_resume, &b_start, &b_q,
-                &b_qgrp, &b_qout, &b_qat, &b_qlen, &b_qoff, &b_qtext, &b_tmatch, &b_tout, &b_xq, &b_xout, &b_runs, &b_batch};
+                &b_qgrp, &b_qout, &b_qat, &b_qlen, &b_qoff, &b_qtext, &b_tmatch, &b_tout, &b_xq, &b_xout, &b_wcall, &b_wq, &b_wout, &b_wtext, &b_wmaps,
+                &b_runs, &b_batch};
     }
     // options.mergeTreeSnapshotChunkSize per document (mt_set_doc_snapshot_chunk; 0 = 10,000)
     std::vector<uint64_t> snap_chunk;
@@ -120,6 +122,15 @@ struct mt_ctx {
     std::vector<uint64_t> tile_off;
     std::vector<uint16_t> range_arena;            // mt_get_text_range's text
     std::vector<uint64_t> range_off;
+    std::vector<mt_walk_rec> walk_recs;           // mt_walk_segments' records, text and distinct maps
+    std::vector<uint64_t> walk_off;
+    std::vector<uint16_t> walk_arena;
+    std::vector<uint32_t> walk_map_doc;
+    std::vector<int32_t> walk_map_ps, walk_map_val;
+    std::vector<uint16_t> walk_map_key;
+    std::vector<uint64_t> walk_map_koff, walk_map_joff;
+    std::string walk_map_json;
+    mt_walk_maps walk_maps{};
     // delta capture (mt_delta_capture / mt_delta_records)
     uint64_t delta_cap = 0, delta_tcap = 0;
     bool delta_valid = false, delta_over = false;

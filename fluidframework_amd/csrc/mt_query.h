@@ -8,6 +8,8 @@
 // and text ranges under any view (mt_get_text_range) over the same scan:
 //   MergeTreeTextHelper.getText           MT/textSegment.ts:163-194 (gatherText :196-284, over
 //                                         mapRange -> nodeMap MT/mergeTree.ts:2927-2994)
+// and segment walks under any view (mt_walk_segments), a record per visited row, over it too:
+//   Client.walkSegments                   MT/client.ts:282-295 (mapRange -> nodeMap, as above)
 // Batched: the host groups the queries by document, one wave takes a document's queries
 // in order (the perspective's U set is reused while consecutive queries share it).  A
 // query reads the document and writes only the wave's U scratch of that document; a tile
@@ -27,6 +29,14 @@
 // range and the view; the count pass and the fill pass of the same scan
 #define MT_QK_TEXT_COUNT (-5)
 #define MT_QK_TEXT_FILL (-6)
+// a segment walk (mt_walk_segments): pos is the query's record in the call's MtWalkCall, which
+// MtState::x_walk names while the walk's launches run (mt_core.h); the count pass and
+// the fill pass of the same scan.  MT_QK_PSET: pos is a property-set id of the document, whose
+// chunks are copied to MtWalkCall::maps from chunk `client` on (the walk's distinct maps, fetched
+// after its fill; no answer record is written).
+#define MT_QK_WALK_COUNT (-7)
+#define MT_QK_WALK_FILL (-8)
+#define MT_QK_PSET (-9)
 #define MT_QT_PRECEDING 0x40000000
 struct __attribute__((aligned(16))) MtQuery { uint32_t doc; int32_t pos, ref, client; };   // ref < 0: local view / kind
 // One answer: the ABI record, where the found row's text sits in the text pool, and the
@@ -39,6 +49,7 @@ struct __attribute__((aligned(16))) MtQueryOut {
 };
 static_assert(sizeof(mt_seg_info) == 64, "mt_seg_info is 16 dwords");
 static_assert(sizeof(mt_tile_rec) == 32, "mt_tile_rec is 8 dwords");
+static_assert(sizeof(mt_walk_rec) == 64, "mt_walk_rec is 16 dwords");
 
 /* ------------------------------------------------------- document-order scan -- */
 // The rows of a document in document order, a unit at a time.  A unit is the up-to-64 rows
@@ -484,11 +495,209 @@ MT_HD unsigned long long mt_text_range_doc(Eng& e, const MtState& S, int start, 
     return done;
 }
 
+/* ---------------------------------------------------------- segment walks -- */
+// walkSegments(handler, start, end) of one document under a view (the rule: include/mtgpu.h): the
+// scan of mt_text_range_doc, entered the same way, with nodeMap's visit test (:2964) as lane
+// data: E - p > 0 && l > 0 && S - p < l, p from the exclusive scan of the lengths under the
+// view.  For S < E the first visited row holds max(S, 0) and the scan runs until the view
+// position reaches E; for S >= E the one row that can pass holds E, and the scan ends with its
+// unit.  A visited row's record goes to rec[popcount of the visited lanes before it]; its
+// obs_pos is the unit's observer start (the cursor's base, kept by every descent mode) plus the
+// exclusive scan of the observer's lengths, which in the local view is p itself.  With text, the
+// visited text rows' whole texts follow each other in the arena, copied one lane per output unit
+// in rounds of 64 as the text fill does.  rec null: count only.  Returns the records; tcount:
+// the text units.  Stores reach rec[0 .. room) and txt[0 .. troom) only; tat: where txt starts
+// in the call's arena (a record's text_off is absolute).
+template <class Eng>
+MT_HD unsigned long long mt_walk_doc(Eng& e, const MtState& S, int start, int end, int ref, int qc, bool text, mt_walk_rec* rec,
+                                     unsigned long long room, uint16_t* txt, unsigned long long tat, unsigned long long troom,
+                                     unsigned long long& tcount) {
+    tcount = 0;
+    if (!mt_tile_blk_ok(e, e.root)) return 0;
+    const bool local = ref < 0;
+    const int r = local ? 0x7FFFFFFF : ref, c = (local || qc < 0 || qc >= MT_NONCOLLAB) ? MT_NOBODY : qc;
+    const int Sx = start == (int)0x80000000 ? 0 : start;
+    int E = end;
+    if (end == (int)0x80000000) E = local ? uni(e.bk(e.root).len) : e.perspectiveLength(r, c);   // undefined: L
+    if (E <= 0) return 0;
+    const bool one = Sx >= E;                       // at most one row, the one holding E
+    const int lo = one ? E : (Sx < 0 ? 0 : Sx);
+    MtTileCursor cur; cur.U = -1; cur.lvl = 0; cur.base = 0;
+    int ubase = 0, s0 = -1, off0 = 0;
+    if (local) {
+        if (lo >= uni(e.bk(e.root).len)) return 0;
+        if (!mt_tile_down(e, cur, e.root, 0, lo, MT_TD_POS)) return 0;
+        ubase = cur.base;
+    } else {
+        int depth = 0;
+        unsigned long long path = 0;
+        s0 = e.containing(lo, r, c, off0, depth, path);
+        if (s0 < 0) return 0;
+        if (!mt_tile_down(e, cur, e.root, 0, 0, MT_TD_PATH, path, depth)) return 0;
+    }
+    unsigned long long done = 0, tdone = 0;
+    const int ttop = e.textTop;
+    for (bool first = true;; first = false) {
+        int height = 0, span = 0;
+        const auto row = mt_tile_unit_rows(e, cur, height, span);
+        // len seq rseq meta | toff props parent tcap | ovl rcl mid
+        const auto q0 = wave_map(span, [&](int t) MT_LAM {
+            const int g = own(row, t);
+            return g >= 0 ? ((const MtQ16a*)&e.row(g))[0] : MtQ16a{0u, 0u, 0u, 0u};
+        });
+        const auto q1 = wave_map(span, [&](int t) MT_LAM {
+            const int g = own(row, t);
+            return g >= 0 ? ((const MtQ16a*)&e.row(g))[1] : MtQ16a{0u, 0u, 0u, 0u};
+        });
+        const auto q2 = wave_map(span, [&](int t) MT_LAM {
+            const int g = own(row, t);
+            return g >= 0 ? ((const MtQ16a*)&e.row(g))[2] : MtQ16a{0u, 0u, 0u, 0u};
+        });
+        const auto vl = wave_map(span, [&](int t) MT_LAM {
+            const MtQ16a a = own(q0, t), x = own(q2, t);
+            const int g = own(row, t), l = (int)a.x;
+            const unsigned long long ovl = (unsigned long long)x.x | ((unsigned long long)x.y << 32);
+            const bool vis = local ? (a.w & MT_M_REMOVED) == 0 : vis_rc((int)a.y, a.w, (int)a.z, x.z, ovl, r, c, e.ovx, e.ovxN, g);
+            return ((g >= 0) & vis & (l > 0)) ? l : 0;
+        });
+        const auto pre = wave_excl_scan(vl);
+        const int vsum = wave_sum(vl);
+        // the observer's lengths: the view's own in the local view
+        const auto opos = local ? pre : wave_excl_scan(wave_map(span, [&](int t) MT_LAM {
+            const MtQ16a a = own(q0, t);
+            return ((own(row, t) >= 0) & ((a.w & MT_M_REMOVED) == 0) & ((int)a.x > 0)) ? (int)a.x : 0;
+        }));
+        if (first && !local) {                      // the unit's start under the view, from the row containing() found
+            const int s = s0;
+            const int t0 = wave_first(wave_map(span, [&](int t) MT_LAM { return own(row, t) == s; }));
+            if (t0 < 0) return 0;
+            ubase = lo - off0 - wave_at(pre, t0);
+        }
+        const int ub = ubase, ob = cur.base;
+        const uint64_t hit = wave_ballot(wave_map(span, [&](int t) MT_LAM {
+            const int p = ub + own(pre, t), l = own(vl, t);
+            return ((E - p > 0) & (l > 0) & (Sx - p < l)) != 0;     // :2964
+        }));
+        // text units per visited row: a text row's whole text
+        const auto olen = wave_map(span, [&](int t) MT_LAM {
+            const bool marker = (own(q0, t).w & MT_M_MARKER) != 0;
+            return (text & ((hit >> t) & 1ull) & !marker) ? own(vl, t) : 0;
+        });
+        const auto opre = wave_excl_scan(olen);
+        const int T = wave_sum(olen);
+        if (rec && hit) {
+            const unsigned long long d0 = done, t0 = tat + tdone;
+            wave_for(span, [&](int t) MT_LAM {
+                const unsigned long long k = d0 + (unsigned long long)__builtin_popcountll(hit & ((1ull << t) - 1ull));
+                if (((hit >> t) & 1ull) && k < room) {          // guards the stores only
+                    const MtQ16a a = own(q0, t), b = own(q1, t), x = own(q2, t);
+                    const bool removed = (a.w & MT_M_REMOVED) != 0, marker = (a.w & MT_M_MARKER) != 0;
+                    const int cl = (int)(a.w & MT_M_CLIENT), p = ub + own(pre, t);
+                    mt_walk_rec w;
+                    w.pos = p; w.start = Sx - p; w.end = E - p; w.len = (int)a.x;
+                    w.seq = (int)a.y; w.client = cl == MT_NONCOLLAB ? -1 : cl;
+                    w.removed_seq = removed ? (int)a.z : (int)0x80000000; w.removed_client = removed ? (int)x.z : -1;
+                    // map: the map's key count for now (the host places the maps' chunks by it, then
+                    // writes the map's index there)
+                    const int ps = (int)b.y;
+                    w.prop_set = ps; w.map = (ps >= 0 && ps < e.psetTop) ? e.pset[ps].n : -1;
+                    w.marker_ref_type = marker ? (int)b.x : -1; w.marker_id = (int)x.w - 1;
+                    w.row = own(row, t); w.obs_pos = ob + own(opos, t);
+                    w.text_off = (text && !marker) ? t0 + (unsigned long long)own(opre, t) : 0ull;
+                    rec[k] = w;
+                }
+            });
+        }
+        if (txt && T > 0) {
+            // the output scan (inclusive) and each row's first source unit, as the text fill keeps them
+            wave_for(MT_WAVE, [&](int t) MT_LAM {
+                e.sc->hold[t] = own(opre, t) + own(olen, t);
+                e.sc->holdLen[t] = (int)own(q1, t).x;
+            });
+            wave_sync();
+            for (int base = 0; base < T; base += MT_WAVE) {
+                const int m = (T - base) < MT_WAVE ? (T - base) : MT_WAVE;
+                const unsigned long long d0 = tdone + (unsigned long long)base;
+                wave_for(m, [&](int k) MT_LAM {
+                    const int j = base + k;
+                    int t = 0;                      // the first row whose inclusive end passes j
+                    for (int step = 32; step; step >>= 1) t += (e.sc->hold[t + step - 1] <= j) ? step : 0;
+                    const int before = e.sc->hold[t ? t - 1 : 0];
+                    const int kk = j - (t ? before : 0), sx = e.sc->holdLen[t];
+                    // the text index clamped to the live half's top; stores bounded by the query's room
+                    int ti = sx + kk;
+                    ti = ti >= ttop ? ttop - 1 : ti;
+                    ti = ti < 0 ? 0 : ti;
+                    const uint16_t v = ttop > 0 ? e.text[ti] : (uint16_t)0;
+                    if (d0 + (unsigned long long)k < troom) txt[d0 + (unsigned long long)k] = v;
+                });
+            }
+            wave_sync();
+        }
+        done += (unsigned long long)__builtin_popcountll(hit);
+        tdone += (unsigned long long)T;
+        if (one) break;
+        ubase += vsum;
+        if (ubase >= E) break;                      // the running view position reached E
+        if (!mt_tile_next(e, cur, 1, !local)) break;    // remote: a row the observer removed may be visible
+        if (local) ubase = cur.base;
+    }
+    tcount = tdone;
+    return done;
+}
+// The chunks of property map ps of the document to maps[dst ..), as far as the map lies below
+// the document's top and the chunks below mcap (else nothing is copied).
+template <class Eng>
+MT_HD void mt_query_pset(Eng& e, MtPSet* maps, unsigned long long mcap, int ps, int dst) {
+    if (!maps || dst < 0 || ps < 0 || ps >= e.psetTop) return;
+    int n = uni(e.pset[ps].n);
+    n = n < 0 ? 0 : (n > MT_PKEYS ? MT_PKEYS : n);
+    const int nch = n > MT_PSK ? (n + MT_PSK - 1) / MT_PSK : 1;
+    if (nch > e.psetTop - ps || (unsigned long long)dst + (unsigned long long)nch > mcap) return;
+    constexpr int W = (int)(sizeof(MtPSet) / 4);
+    int* to = (int*)(maps + dst);
+    for (int base = 0; base < nch * W; base += MT_WAVE) {
+        const int m = (nch * W - base) < MT_WAVE ? (nch * W - base) : MT_WAVE;
+        wave_for(m, [&](int k) MT_LAM { to[base + k] = ((const int*)(e.pset + ps))[base + k]; });
+    }
+    wave_sync();
+}
+
 template <class Eng>
 MT_HD void mt_query_run(Eng& e, const MtState& S, const MtQuery* q, uint32_t q0, uint32_t q1, MtQueryOut* out) {
     MtTileMemo memo; memo.lab = -1; memo.ps = -1; memo.res = false;
     for (uint32_t i = q0; i < q1; i++) {
         const int pos = uni(q[i].pos), ref = uni(q[i].ref), qc = uni(q[i].client);
+        if (ref <= MT_QK_WALK_COUNT) {              // a segment walk: its record holds the query and takes the counts
+            const MtWalkCall* wc = S.x_walk;
+            if (!wc) continue;
+            if (ref == MT_QK_PSET) {
+                mt_query_pset(e, (MtPSet*)uni64((unsigned long long)wc->maps), uni64(wc->mcap), pos, qc);
+                continue;
+            }
+            const bool fill = ref == MT_QK_WALK_FILL;
+            MtWalkQ* wq = (MtWalkQ*)uni64((unsigned long long)wc->q);
+            mt_walk_rec* wout = (mt_walk_rec*)uni64((unsigned long long)wc->out);
+            const unsigned long long wcap = uni64(wc->cap);
+            if (!wq || (uint32_t)pos >= uni(wc->nq)) continue;
+            MtWalkQ& x = wq[(uint32_t)pos];
+            const bool text = (uni(wc->flags) & MT_WALK_TEXT) != 0;
+            const unsigned long long at = uni64(x.at), cap = uni64(x.count), tat = uni64(x.tat), tcap = uni64(x.tcount);
+            unsigned long long room = (fill && wout && at < wcap) ? wcap - at : 0ull;
+            room = room < cap ? room : cap;
+            unsigned long long troom = (fill && text && S.x_out && tat < S.x_cap) ? S.x_cap - tat : 0ull;
+            troom = troom < tcap ? troom : tcap;
+            unsigned long long tcnt = 0;
+            const unsigned long long cnt = mt_walk_doc(e, S, uni(x.start), uni(x.end), uni(x.ref), uni(x.client), text,
+                                                       room ? wout + at : nullptr, room, troom ? S.x_out + tat : nullptr, tat,
+                                                       troom, tcnt);
+            MtWalkQ* xp = &x;
+            wave_for(1, [&](int) MT_LAM {
+                if (fill) { xp->filled = cnt; xp->tfilled = tcnt; } else { xp->count = cnt; xp->tcount = tcnt; }
+            });
+            wave_sync();
+            continue;
+        }
         if (ref <= MT_QK_TEXT_COUNT) {              // a text range: its record holds the query and takes the count
             const bool fill = ref == MT_QK_TEXT_FILL;
             if (!S.x_q || (uint32_t)pos >= S.x_nq) continue;

@@ -62,6 +62,12 @@ class MtTileLabels(ctypes.Structure):
                 ("match", ctypes.c_void_p)]
 
 
+class MtWalkMaps(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_uint32), ("doc", ctypes.c_void_p), ("prop_set", ctypes.c_void_p),
+                ("key_off", ctypes.c_void_p), ("key", ctypes.c_void_p), ("value", ctypes.c_void_p),
+                ("json_off", ctypes.c_void_p), ("json", ctypes.c_void_p)]
+
+
 def _bind(lib, prefix: str):
     P, U32, I32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32
 
@@ -135,6 +141,8 @@ def _bind(lib, prefix: str):
                                                   ctypes.POINTER(P)]),
         get_text_range=f("get_text_range", ctypes.c_int, [P, U32, P, P, P, P, P, P, U32, ctypes.POINTER(P),
                                                           ctypes.POINTER(P)]),
+        walk_segments=f("walk_segments", ctypes.c_int, [P, U32, P, P, P, P, P, U32, ctypes.POINTER(P), ctypes.POINTER(P),
+                                                        ctypes.POINTER(P), ctypes.POINTER(P)]),
         set_doc_snapshot_chunk=f("set_doc_snapshot_chunk", ctypes.c_int, [P, U32, P, P]),
         reserve_staging=f("reserve_staging", ctypes.c_int, [P, ctypes.c_uint64]),
         docs_resize=f("docs_resize", ctypes.c_int, [P, U32, P, P]),
@@ -157,6 +165,10 @@ SEG_INFO_DTYPE = np.dtype([(f, np.uint32 if f.startswith("path") else np.int32) 
 POS_UNDEFINED = -(1 << 31)              # MT_POS_UNDEFINED
 TILE_REC_DTYPE = np.dtype([(f, np.int32) for f in ("pos", "text_pos", "row", "prop_set", "ref_type", "marker_id",
                                                    "pad0", "pad1")])    # mt_tile_rec
+WALK_REC_DTYPE = np.dtype([(f, np.int32) for f in ("pos", "start", "end", "len", "seq", "client", "removed_seq",
+                                                   "removed_client", "prop_set", "map", "marker_ref_type", "marker_id",
+                                                   "row", "obs_pos")] + [("text_off", np.uint64)])    # mt_walk_rec
+MT_WALK_TEXT = 1
 MT_CHUNK_INFINITY = (1 << 64) - 1      # mt_set_doc_snapshot_chunk: Infinity (one chunk)
 MT_CHUNK_NONE = (1 << 64) - 2          # a size no length is below (0, negative, NaN)
 MT_PARTITION_AUTO = 0xFFFFFFFF         # mt_set_partition: chosen per batch (mt_plan_partition)
@@ -706,12 +718,86 @@ class Engine:
         raw = ctypes.string_at(arena, int(offs[-1]) * 2) if offs[-1] else b""
         return [raw[2 * offs[i]:2 * offs[i + 1]].decode("utf-16-le", "surrogatepass") for i in range(n)]
 
+    def walk_segments(self, docs, start=None, end=None, ref_seq=None, client=None, text: bool = True) -> "Walk":
+        """mt_walk_segments: the segments Client.walkSegments(handler, start[i], end[i]) visits
+        (MT/client.ts:282-295 -> mapRange -> nodeMap, MT/mergeTree.ts:2927-2994; the rule:
+        include/mtgpu.h) under (ref_seq[i], client[i]), one record each, gathered on the device.
+        start / end, ref_seq / client as get_text_range takes them; text False: no text is
+        copied.  Returns a Walk: query i is walk[i] = (its WALK_REC_DTYPE records, their texts,
+        their property maps).  Raw ABI: client is the engine's per-document client index."""
+        d = _u32(docs)
+        n = len(d)
+
+        def arr(a):
+            if a is None:
+                return None
+            return _i32([POS_UNDEFINED if x is None else int(x) for x in np.broadcast_to(np.asarray(a, object), (n,))])
+        s, e = arr(start), arr(end)
+        r = None if ref_seq is None else _i32(np.broadcast_to(np.asarray(ref_seq), (n,)))
+        c = None if client is None else _i32(np.broadcast_to(np.asarray(client), (n,)))
+        recs, off, arena, maps = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        ptr = lambda a: a.ctypes.data if a is not None and len(a) else None  # noqa: E731
+        self._check(self.fn["walk_segments"](self.h, n, ptr(d), ptr(s), ptr(e), ptr(r), ptr(c), MT_WALK_TEXT if text else 0,
+                                             ctypes.byref(recs), ctypes.byref(off), ctypes.byref(arena) if text else None,
+                                             ctypes.byref(maps)), "mt_walk_segments")
+        return Walk(self, n, recs, off, arena if text else None, maps)
+
     def dump(self, doc: int) -> np.ndarray:
         rows, n = ctypes.c_void_p(), ctypes.c_uint32()
         self._check(self.fn["dump_segments"](self.h, doc, ctypes.byref(rows), ctypes.byref(n)), "mt_dump_segments")
         a = np.frombuffer(ctypes.string_at(rows, n.value * 48), np.int32).reshape(-1, 12).copy()
         self.fn["free"](rows)
         return a
+
+
+class Walk:
+    """The answer of Engine.walk_segments, copied out of the library's arrays: `recs` (every
+    query's WALK_REC_DTYPE records), `off` (query i owns recs[off[i]:off[i + 1]]), `units` (the
+    text arena's UTF-16 units, None without text), `maps` (the distinct property maps the records'
+    `map` fields index, decoded as Engine.pset_dict decodes them) and `maps_json` (each map's JSON
+    object text, as the segment JSON's "props" member)."""
+
+    def __init__(self, eng, n, recs, off, arena, maps):
+        from .batch import decode_value
+        u64 = ctypes.POINTER(ctypes.c_uint64)
+        self.off = np.ctypeslib.as_array(ctypes.cast(off, u64), (n + 1,)).copy()
+        total = int(self.off[-1])
+        self.recs = (np.frombuffer(ctypes.string_at(recs, total * WALK_REC_DTYPE.itemsize), WALK_REC_DTYPE).copy()
+                     if total else np.zeros(0, WALK_REC_DTYPE))
+        self.units = None
+        if arena is not None:
+            t = self.recs[self.recs["marker_ref_type"] < 0]
+            nu = int((t["text_off"] + t["len"].astype(np.uint64)).max()) if len(t) else 0
+            self.units = np.frombuffer(ctypes.string_at(arena, 2 * nu), np.uint16).copy() if nu else np.zeros(0, np.uint16)
+        m = ctypes.cast(maps, ctypes.POINTER(MtWalkMaps)).contents
+        self.maps, self.maps_json = [], []
+        if m.n:
+            ko = np.ctypeslib.as_array(ctypes.cast(m.key_off, u64), (m.n + 1,))
+            jo = np.ctypeslib.as_array(ctypes.cast(m.json_off, u64), (m.n + 1,))
+            keys = np.frombuffer(ctypes.string_at(m.key, 2 * int(ko[-1])), np.uint16)
+            vals = np.frombuffer(ctypes.string_at(m.value, 4 * int(ko[-1])), np.int32)
+            js = ctypes.string_at(m.json, int(jo[-1]))
+            for k in range(m.n):
+                a, b = int(ko[k]), int(ko[k + 1])
+                self.maps.append({eng.props.keys[int(x)]: decode_value(int(v), eng.props.values_json)
+                                  for x, v in zip(keys[a:b], vals[a:b])})
+                self.maps_json.append(js[int(jo[k]):int(jo[k + 1])].decode("utf-8", "surrogatepass"))
+
+    def __len__(self):
+        return len(self.off) - 1
+
+    def text(self, k: int):
+        """Record k's text (None: a marker, or a walk without text)."""
+        r = self.recs[k]
+        if self.units is None or r["marker_ref_type"] >= 0:
+            return None
+        a = int(r["text_off"])
+        return self.units[a:a + int(r["len"])].tobytes().decode("utf-16-le", "surrogatepass")
+
+    def __getitem__(self, i: int):
+        a, b = int(self.off[i]), int(self.off[i + 1])
+        return (self.recs[a:b], [self.text(k) for k in range(a, b)],
+                [self.maps[m] if m >= 0 else None for m in self.recs["map"][a:b]])
 
 
 @dataclass
@@ -784,6 +870,28 @@ class Segment:
             self.text, self.properties = j["text"], props
         self._obs_pos = int(info["obs_pos"])
         self._doc, self._version = client.doc_id, version
+
+    @classmethod
+    def of_walk(cls, rec, text, props, props_json, client, version: int) -> "Segment":
+        """The same copy from one mt_walk_segments record, its text and its property map."""
+        s = object.__new__(cls)
+        s.cachedLength, s.seq = int(rec["len"]), int(rec["seq"])
+        s.clientId = client._short_of(int(rec["client"]))
+        rs = int(rec["removed_seq"])
+        s.removedSeq = None if rs == POS_UNDEFINED else rs
+        s.removedClientId = client._short_of(int(rec["removed_client"])) if s.removedSeq is not None else None
+        pj = None if props_json is None else json.loads(props_json)
+        if int(rec["marker_ref_type"]) >= 0:
+            s.text, s.refType, s.properties = None, int(rec["marker_ref_type"]), props
+            s._json = {"marker": {"refType": s.refType}}
+            if pj is not None:
+                s._json["props"] = pj
+        else:
+            s.text, s.properties = text, props
+            s._json = text if pj is None else {"text": text, "props": pj}
+        s._obs_pos = int(rec["obs_pos"])
+        s._doc, s._version = client.doc_id, version
+        return s
 
     def toJSONObject(self):
         return self._json
@@ -880,6 +988,29 @@ class MergeTreeClient:
     def createTextHelper(self) -> "TextHelper":
         """Client.createTextHelper (client.ts): MergeTreeTextHelper over this document."""
         return TextHelper(self)
+
+    def walkSegments(self, handler, start=None, end=None, accum=None, splitRange=False) -> None:
+        """Client.walkSegments(handler, start, end, accum, splitRange) (MT/client.ts:282-295):
+        handler(segment, pos, refSeq, clientId, start, end, accum) for every segment nodeMap
+        visits (MT/mergeTree.ts:2964), in order, until it returns something falsy (None
+        included: `go = actions.leaf(...)`, :2979).  refSeq is getCurrentSeq(), clientId the
+        observer's short id 0; start and end are relative to the segment and unclipped.  The
+        segments are copies, as getContainingSegment's.  splitRange would split the observer's
+        own tree (ensureIntervalBoundary, :2820-2827) and is refused: DESIGN.md §7."""
+        if splitRange:
+            raise MergeTreeError("walkSegments: splitRange (ensureIntervalBoundary writes to the tree) is not "
+                                 "reproduced: DESIGN.md §7")
+        self.group.flush()
+        self._raise_status()
+        w = self.engine.walk_segments([self.doc_id], [start], [end])
+        ref = self.getCurrentSeq()
+        for k in range(len(w.recs)):
+            r = w.recs[k]
+            m = int(r["map"])
+            seg = Segment.of_walk(r, w.text(k), w.maps[m] if m >= 0 else None, w.maps_json[m] if m >= 0 else None, self,
+                                  self.group.version)
+            if not handler(seg, int(r["pos"]), ref, 0, int(r["start"]), int(r["end"]), accum):
+                break
 
     def snapshot(self, catchUpMsgs: list | None = None, min_seq: int | None = None, seq: int | None = None) -> dict:
         """Client.snapshot (client.ts:923-956) as an ITree.  options

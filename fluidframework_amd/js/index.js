@@ -331,6 +331,36 @@ class Engine {
         return addon.getTextRange(this.h, Uint32Array.from(docs), arr(start, -(2 ** 31)), arr(end, -(2 ** 31)), arr(refSeq, -1),
             arr(client, -1), String(placeholder));
     }
+    /**
+     * mt_walk_segments: the segments Client.walkSegments(handler, start[i], end[i]) visits
+     * (MT/client.ts:282-295; nodeMap's visit test MT/mergeTree.ts:2964; the rule: include/mtgpu.h)
+     * under (refSeq[i], client[i]), gathered on the device.  Arguments as getTextRange's; text
+     * false: no text is copied.  Returns typed arrays, no object per record:
+     * { recs: Int32Array (16 per record: pos, start, end, len, seq, client, removedSeq,
+     * removedClient, propSet, map, markerRefType, markerId, row, obsPos, then textOff's low and
+     * high words), off: record offsets, docs.length + 1, units: Uint16Array of the text arena
+     * (record k's text: units [textOff, textOff + len)), maps: { doc, propSet, keyOff, keys,
+     * values, json: [the distinct maps' JSON object texts] } }.  Raw ABI, as getTextRange.
+     */
+    walkSegments(docs, start, end, refSeq, client, text = true) {
+        const n = docs.length;
+        const arr = (a, undef) => Int32Array.from({ length: n }, (_, i) => {
+            const v = a === undefined ? undefined : a[i];
+            if (v === undefined) return undef;
+            if (typeof v !== "number" || !Number.isInteger(v)) throw new TypeError(`walkSegments: ${String(v)} is not an integer`);
+            return Math.max(-(2 ** 31) + 1, Math.min(2 ** 31 - 1, v));
+        });
+        return addon.walkSegments(this.h, Uint32Array.from(docs), arr(start, -(2 ** 31)), arr(end, -(2 ** 31)), arr(refSeq, -1),
+            arr(client, -1), text ? 1 : 0);
+    }
+    /** The plain object of map m of a walkSegments answer, decoded as psetObject decodes. */
+    walkMapObject(maps, m) {
+        const o = {};
+        for (let k = maps.keyOff[m]; k < maps.keyOff[m + 1]; k++) {
+            o[this.props.keys[maps.keys[k]]] = decodeValue(maps.values[k], this.props.valueJson);
+        }
+        return o;
+    }
     /** Record the delta / maintenance callbacks of later batches (mt_delta_capture; 0: off). */
     deltaCapture(capacity) { addon.deltaCapture(this.h, capacity); }
     /** The last batch's records: Int32Array, 8 per record (op, kind, pos, len, seg, a, b, pad). */
@@ -505,6 +535,49 @@ class MergeTreeClient {
         else if (j.marker) seg.refType = j.marker.refType;
         else seg.text = j.text;
         return seg;
+    }
+    /**
+     * Client.walkSegments(handler, start, end, accum, splitRange) (client.ts:282-295):
+     * handler(segment, pos, refSeq, clientId, start, end, accum) for every segment nodeMap
+     * visits (mergeTree.ts:2964), in order, until it returns something falsy (undefined
+     * included: `go = actions.leaf(...)`, :2979).  refSeq is getCurrentSeq(), clientId the
+     * observer's short id 0; start and end are relative to the segment and unclipped.  The
+     * segments are copies as getContainingSegment's.  splitRange would split the observer's
+     * own tree (ensureIntervalBoundary, :2820-2827) and is refused: DESIGN.md §7.
+     */
+    walkSegments(handler, start, end, accum, splitRange = false) {
+        if (splitRange) throw new Error("walkSegments: splitRange (ensureIntervalBoundary writes to the tree) is not reproduced: DESIGN.md §7");
+        this.group.flush();
+        this.checkStatus();
+        const engine = this.group.engine;
+        const w = engine.walkSegments([this.docId], [start], [end]);
+        const shortOf = (i) => (i < 0 ? -2 : i + 1);                // NonCollabClient = -2
+        const objs = new Map();
+        for (let k = 0; k < w.off[1]; k++) {
+            const r = w.recs.subarray(16 * k, 16 * k + 16);
+            const m = r[9];
+            if (m >= 0 && !objs.has(m)) objs.set(m, engine.walkMapObject(w.maps, m));
+            const marker = r[10] >= 0;
+            const at = (r[14] >>> 0) + (r[15] >>> 0) * 2 ** 32;
+            let text;
+            if (!marker) {
+                text = "";
+                for (let a = at; a < at + r[3]; a += 8192) text += String.fromCharCode.apply(null, w.units.subarray(a, Math.min(a + 8192, at + r[3])));
+            }
+            const props = m >= 0 ? JSON.parse(w.maps.json[m]) : undefined;
+            let j;
+            if (marker) j = props === undefined ? { marker: { refType: r[10] } } : { marker: { refType: r[10] }, props };
+            else j = props === undefined ? text : { text, props };
+            const seg = {
+                cachedLength: r[3], seq: r[4], clientId: shortOf(r[5]),
+                removedSeq: r[6] === -(2 ** 31) ? undefined : r[6],
+                removedClientId: r[6] === -(2 ** 31) ? undefined : shortOf(r[7]),
+                properties: m >= 0 ? objs.get(m) : undefined,
+                toJSONObject: () => j, _obsPos: r[13], _version: this.group.version,
+            };
+            if (marker) seg.refType = r[10]; else seg.text = text;
+            if (!handler(seg, r[0], this.currentSeq, 0, r[1], r[2], accum)) break;
+        }
     }
     /**
      * Client.findTile (client.ts:1095-1098; MergeTree.findTile, mergeTree.ts:1752-1778) in the
@@ -793,6 +866,8 @@ class SequenceChannel {
     // SharedString's text reads (sequence/src/sharedString.ts:211-225): the collab window's
     // (currentSeq, clientId) is the local view
     getText(start, end) { return this.client.getText(start, end); }
+    /** SharedSegmentSequence.walkSegments (sequence/src/sequence.ts:373-378). */
+    walkSegments(handler, start, end, accum, splitRange = false) { this.client.walkSegments(handler, start, end, accum, splitRange); }
     getTextWithPlaceholders() { return this.client.createTextHelper().getText(this.client.currentSeq, 0, " "); }
     getTextRangeWithPlaceholders(start, end) { return this.client.createTextHelper().getText(this.client.currentSeq, 0, " ", start, end); }
     getTextRangeWithMarkers() {

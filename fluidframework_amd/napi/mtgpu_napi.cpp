@@ -661,6 +661,66 @@ napi_value GetTextRange(napi_env env, napi_callback_info info) {
     return out;
 }
 
+// walkSegments(ctx, docs, start, end, refSeq, client: Int32Array, flags) -> { recs: Int32Array (16
+// per record, mt_walk_rec as it lies), off: Float64Array, units: Uint16Array (the text arena),
+// maps: { doc: Uint32Array, propSet: Int32Array, keyOff: Float64Array, keys: Uint16Array, values:
+// Int32Array, json: [string per distinct map] } } (mt_walk_segments): typed arrays, no object per
+// record; INT32_MIN in start / end is undefined, refSeq < 0 the local view
+napi_value WalkSegments(napi_env env, napi_callback_info info) {
+    napi_value argv[7];
+    if (!get_args(env, info, 7, argv)) return nullptr;
+    mt_ctx* c = get_ctx(env, argv[0]); if (!c) return nullptr;
+    const uint32_t* docs; const int32_t *st, *en, *ref, *cli; size_t n, n1, n2, n3, n4;
+    if (!typed(env, argv[1], napi_uint32_array, &docs, &n) || !typed(env, argv[2], napi_int32_array, &st, &n1) ||
+        !typed(env, argv[3], napi_int32_array, &en, &n2) || !typed(env, argv[4], napi_int32_array, &ref, &n3) ||
+        !typed(env, argv[5], napi_int32_array, &cli, &n4)) return nullptr;
+    if (n1 < n || n2 < n || n3 < n || n4 < n) { napi_throw_range_error(env, nullptr, "start/end/refSeq/client shorter than docs"); return nullptr; }
+    uint32_t flags = 0;
+    if (napi_get_value_uint32(env, argv[6], &flags) != napi_ok) { napi_throw_type_error(env, nullptr, "flags is not a number"); return nullptr; }
+    const mt_walk_rec* recs = nullptr; const uint64_t* off = nullptr; const uint16_t* arena = nullptr; const mt_walk_maps* maps = nullptr;
+    int rc = mt_walk_segments(c, (uint32_t)n, docs, st, en, ref, cli, flags, &recs, &off, (flags & MT_WALK_TEXT) ? &arena : nullptr, &maps);
+    if (rc) return throw_rc(env, c, rc, "mt_walk_segments");
+    static_assert(sizeof(mt_walk_rec) == 64, "mt_walk_rec is 16 dwords");
+    const size_t total = (size_t)off[n];
+    size_t units = 0;
+    if (arena) for (size_t k = 0; k < total; k++) if (recs[k].marker_ref_type < 0) { const size_t e = (size_t)recs[k].text_off + (size_t)recs[k].len; units = e > units ? e : units; }
+    auto f64 = [&](const uint64_t* src, size_t m) {
+        napi_value ab, ta; void* d = nullptr;
+        napi_create_arraybuffer(env, 8 * m, &d, &ab);
+        for (size_t i = 0; i < m; i++) ((double*)d)[i] = (double)src[i];
+        napi_create_typedarray(env, napi_float64_array, m, ab, 0, &ta);
+        return ta;
+    };
+    auto u16 = [&](const uint16_t* src, size_t m) {
+        napi_value ab, ta; void* d = nullptr;
+        napi_create_arraybuffer(env, 2 * m, &d, &ab);
+        if (m) memcpy(d, src, 2 * m);
+        napi_create_typedarray(env, napi_uint16_array, m, ab, 0, &ta);
+        return ta;
+    };
+    napi_value o, mo, js;
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "recs", make_i32(env, (const int32_t*)recs, 16 * total));
+    napi_set_named_property(env, o, "off", f64(off, n + 1));
+    napi_set_named_property(env, o, "units", u16(arena, units));
+    napi_create_object(env, &mo);
+    const size_t nm = maps->n, nk = (size_t)maps->key_off[nm];
+    napi_set_named_property(env, mo, "doc", make_u32(env, maps->doc, nm));
+    napi_set_named_property(env, mo, "propSet", make_i32(env, maps->prop_set, nm));
+    napi_set_named_property(env, mo, "keyOff", f64(maps->key_off, nm + 1));
+    napi_set_named_property(env, mo, "keys", u16(maps->key, nk));
+    napi_set_named_property(env, mo, "values", make_i32(env, maps->value, nk));
+    napi_create_array_with_length(env, nm, &js);
+    for (size_t m = 0; m < nm; m++) {
+        napi_value s;
+        napi_create_string_utf8(env, maps->json + maps->json_off[m], (size_t)(maps->json_off[m + 1] - maps->json_off[m]), &s);
+        napi_set_element(env, js, (uint32_t)m, s);
+    }
+    napi_set_named_property(env, mo, "json", js);
+    napi_set_named_property(env, o, "maps", mo);
+    return o;
+}
+
 // deltaCapture(ctx, capacity): record the delta / maintenance callbacks of later batches
 napi_value DeltaCapture(napi_env env, napi_callback_info info) {
     napi_value argv[2];
@@ -849,6 +909,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"findTile", nullptr, FindTile, nullptr, nullptr, nullptr, kQuiet, nullptr},
         {"tileIndex", nullptr, TileIndex, nullptr, nullptr, nullptr, kQuiet, nullptr},
         {"getTextRange", nullptr, GetTextRange, nullptr, nullptr, nullptr, kQuiet, nullptr},
+        {"walkSegments", nullptr, WalkSegments, nullptr, nullptr, nullptr, kQuiet, nullptr},
     };
     napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
     return exports;

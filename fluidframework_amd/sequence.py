@@ -247,6 +247,10 @@ class SequenceDoc:
     def getText(self, start=None, end=None) -> str:
         return self.client.getText(start, end)
 
+    def walkSegments(self, handler, start=None, end=None, accum=None, splitRange=False) -> None:
+        """SharedSegmentSequence.walkSegments (sequence/src/sequence.ts:373-378)."""
+        self.client.walkSegments(handler, start, end, accum, splitRange)
+
     def getTextWithPlaceholders(self) -> str:
         return self.client.createTextHelper().getText(self.client.current_seq, 0, " ")
 

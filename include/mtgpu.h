@@ -687,6 +687,90 @@ int  mt_get_text_range(mt_ctx* ctx, uint32_t n, const uint32_t* doc_ids,
                        const uint16_t* placeholder, uint32_t placeholder_len,
                        const uint16_t** arena, const uint64_t** off);
 
+/*
+ * The segments of a range under any view, gathered on the device.
+ *   Client.walkSegments(handler, start?, end?, accum?, splitRange?)   MT/client.ts:282-295
+ *   mapRange -> nodeMap        MT/mergeTree.ts:2819-2829, :2927-2994 (the visit test :2964)
+ *   nodeLength                 MT/mergeTree.ts:1652-1692 (the local client :1653-1659)
+ *   SharedSegmentSequence.walkSegments   sequence/src/sequence.ts:373-378
+ * The view is (ref_seq[i], client[i]) as mt_get_text_range takes it: ref_seq < 0, or ref_seq /
+ * client NULL, is the local view; a remote view is any valid perspective.
+ * Number the document's rows in order; l_i is row i's length under the view, p_i the sum of
+ * the l before it, L the sum of all.  S = start[i] (undefined: 0), E = end[i] (undefined: L,
+ * as nodeMap sets _end = blockLength of the root, :2936-2938).
+ * nodeMap visits row i when E - p_i > 0 && l_i > 0 && S - p_i < l_i (:2964), in document
+ * order, and calls leaf(segment, pos = p_i, refSeq, clientId, start = S - p_i, end = E - p_i,
+ * accum).  The relative start and end are passed unclipped: start may be negative and end may
+ * exceed the segment's length.  Each visit is one record.  So:
+ *   S < E:   the visited rows are those whose [p_i, p_i + l_i) intersects [S, E).  A row that
+ *            ends exactly at S or begins exactly at E is not visited.  S < 0 acts as below 0;
+ *            E <= 0 or S >= L visits nothing.
+ *   S >= E:  at most one row is visited: a row with p_i < E and S < p_i + l_i.  Such a row is
+ *            always a text row of length >= 2 (S == E) or >= 3 (S > E); its record has
+ *            start >= end.  As with text ranges this depends on how the text is segmented; it
+ *            is the reference's behaviour and is reproduced from the rows as they are.
+ *   Markers are visited like any row of length 1.
+ *   Rows invisible under the view are never visited.  Under a remote view a visited row may
+ *   be one the observer has since removed; its record then carries removed_seq and
+ *   removed_client, and obs_pos is where the observer's getPosition puts the removed row.
+ * The handler's return value stops the walk (go = actions.leaf(...), :2975, :2979): a handler
+ * that returns nothing stops it after the first segment.  That is the hosts' part; this call
+ * returns every visited row.
+ * Not reproduced: splitRange.  mapRange then runs ensureIntervalBoundary(start) and (end)
+ * first (:2820-2827), which splits segments of the tree: a passive observer that splits its
+ * own tree is no longer bit-exact with the streams it replays.  There is no such flag here,
+ * and the hosts refuse a truthy splitRange.  The rule was derived by reading the reference,
+ * which could not be executed (client.walkSegments.spec.ts:22-47 pins two cases).
+ *
+ * Query i is answered by recs[rec_off[i] .. rec_off[i+1]).  With MT_WALK_TEXT and text_arena
+ * not NULL, a visited text row's whole text is units [text_off, text_off + len) of
+ * *text_arena (whole, not clipped to the range; markers have none).  maps (NULL: not wanted)
+ * receives the distinct (document, prop_set) pairs the records name; a record's `map` indexes
+ * them.  Map m's keys and interned value ids are key / value [key_off[m] .. key_off[m+1]) in
+ * insertion order, as mt_doc_pset gives them, and bytes [json_off[m], json_off[m+1]) of json
+ * are its JSON object text (the "props" member of the segment's toJSONObject form,
+ * textSegment.ts:48-54, mergeTree.ts:649-653), so a host builds a segment from its record, the
+ * arena and the map without another call.  All arrays are library-owned and valid until the
+ * next mt_walk_segments; the arenas of other calls are not touched.  Queries may repeat a
+ * document and come in any order; one document's queries run in order in one wave.  start /
+ * end NULL: all 0 / all undefined; an element MT_POS_UNDEFINED: undefined; any other value
+ * outside [-2^30, 2^30] is MT_E_INVALID (S - p_i cannot overflow; no document is that long).
+ * More than 2^31 records or text units in one call is MT_E_INVALID: split the call.  Nothing
+ * of a document is modified: a remote view writes only the wave's perspective scratch, as
+ * position queries do, a local view nothing.  Documents whose status word is set are read as
+ * they stand.  Two device passes over the same scan (count, then fill) and one launch that
+ * copies the distinct maps.
+ */
+typedef struct mt_walk_rec {        /* 64 bytes */
+    int32_t pos, start, end, len;   /* p_i, S - p_i, E - p_i, cachedLength                     */
+    int32_t seq, client;            /* insertion seq; client index (-1: NonCollabClient)       */
+    int32_t removed_seq;            /* INT32_MIN: undefined                                    */
+    int32_t removed_client;         /* -1 when not removed                                     */
+    int32_t prop_set;               /* the document's property-set id, -1: undefined           */
+    int32_t map;                    /* index into this call's distinct maps, -1: none          */
+    int32_t marker_ref_type;        /* -1: text segment                                        */
+    int32_t marker_id;              /* per-document index of its markerId, -1: none            */
+    int32_t row;                    /* engine row id                                           */
+    int32_t obs_pos;                /* the segment's start in the local view (getPosition)     */
+    uint64_t text_off;              /* text rows, with MT_WALK_TEXT: where its text starts     */
+} mt_walk_rec;
+typedef struct mt_walk_maps {
+    uint32_t n;                     /* distinct maps                                           */
+    const uint32_t* doc;            /* [n] the document                                        */
+    const int32_t* prop_set;        /* [n] its property-set id there                           */
+    const uint64_t* key_off;        /* [n + 1]                                                 */
+    const uint16_t* key;            /* key ids, insertion order                                */
+    const int32_t* value;           /* interned value ids (negative: as mt_doc_pset)           */
+    const uint64_t* json_off;       /* [n + 1]                                                 */
+    const char* json;
+} mt_walk_maps;
+#define MT_WALK_TEXT 1u
+int  mt_walk_segments(mt_ctx* ctx, uint32_t n, const uint32_t* doc_ids,
+                      const int32_t* start, const int32_t* end,
+                      const int32_t* ref_seq, const int32_t* client, uint32_t flags,
+                      const mt_walk_rec** recs, const uint64_t** rec_off,
+                      const uint16_t** text_arena, const mt_walk_maps** maps);
+
 /* Client long-id strings (JSON literals) by per-document client index; used for
  * the snapshot's "client"/"removedClient" fields (snapshotV1.ts:229, :237). */
 int  mt_set_client_names(mt_ctx* ctx, uint32_t n, const char* const* client_json);
