@@ -1329,9 +1329,69 @@ int MT_FN(tile_index)(mt_ctx* c, uint32_t n, const uint32_t* docs, const uint32_
     return MT_OK;
 }
 
-// Text ranges (mt_query.h): the records go up once per pass (the fill's carry the offsets the
-// counts gave), the text comes down once.  The query kernel's answer records are not used by the
-// text kinds, so none is allocated or downloaded.
+// The range queries (mt_query.h: text ranges and segment walks, two visitors of one scan) share
+// their records and the two passes over them: the queries staged by document once, the records up
+// once per pass (the fill's carry the offsets the counts gave: off[i] for query i's answer, and the
+// same for a walk's text), each pass one launch of the query kernel, with `count_kind` and then the
+// fill kind below it.  The kernel's answer records are not used by the range kinds, so none is
+// allocated or downloaded.  call: a walk's MtWalkCall (it lives in device memory, reached through
+// x_walk: MtState does not grow, mt_core.h), whose fill writes records to b_wout and text to
+// b_wtext; null for a text range, whose fill writes its units to b_xout.  total / ttotal: the
+// answers' and the walk's text's lengths.  Every return path clears what it set in MtState.
+static int mt_range_passes(mt_ctx* c, const std::string& what, const char* capped, uint32_t n, const uint32_t* docs,
+                           const int32_t* start, const int32_t* end, const int32_t* ref, const int32_t* cli, int count_kind,
+                           MtWalkCall* call, uint64_t* off, uint64_t& total, uint64_t& ttotal) {
+    if (n > 0x7FFFFFFFu) { c->err = what + ": too many queries"; return MT_E_INVALID; }
+    std::vector<MtRangeQ> x(n, MtRangeQ{});
+    for (uint32_t i = 0; i < n; i++) {
+        x[i].start = start ? start[i] : 0; x[i].end = end ? end[i] : MT_POS_UNDEFINED;
+        x[i].ref = (ref && ref[i] >= 0) ? ref[i] : -1; x[i].client = cli ? cli[i] : -1;
+    }
+    std::vector<uint32_t> ord;
+    std::vector<MtQuery> q;
+    uint32_t ng = 0;
+    int rc;
+    if ((rc = mt_stage_queries(c, n, docs, nullptr, nullptr, nullptr, count_kind, ord, q, ng))) return rc;
+    if ((rc = mtb_ensure(c, c->b_xq, sizeof(MtRangeQ) * n))) return rc;
+    if (call && (rc = mtb_ensure(c, c->b_wcall, sizeof(MtWalkCall)))) return rc;
+    auto done = [&](int r) { c->S.x_q = nullptr; c->S.x_nq = 0; c->S.x_out = nullptr; c->S.x_cap = 0; return r; };
+    auto pass = [&](std::vector<MtRangeQ>& y) {     // the records and the call up, one launch, the records down to y
+        mtb_h2d(c, c->b_xq.p, x.data(), sizeof(MtRangeQ) * n);
+        if (call) mtb_h2d(c, c->b_wcall.p, call, sizeof *call);
+        int r = mtb_launch_query(c, (const MtQuery*)c->b_q.p, (const uint32_t*)c->b_qgrp.p, (MtQueryOut*)c->b_qout.p, ng);
+        if (!r) r = mtb_sync(c);
+        if (!r) mtb_d2h(c, y.data(), c->b_xq.p, sizeof(MtRangeQ) * n);
+        return r;
+    };
+    done(MT_OK);
+    if (call) { call->q = (MtRangeQ*)c->b_xq.p; call->nq = n; c->S.x_walk = (const MtWalkCall*)c->b_wcall.p; }
+    else { c->S.x_q = (MtRangeQ*)c->b_xq.p; c->S.x_nq = n; }
+    if ((rc = pass(x))) return done(rc);
+    total = ttotal = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        x[i].at = total; x[i].tat = ttotal; off[i] = total;
+        total += x[i].count; ttotal += x[i].tcount;
+        if (total > 0x80000000ull || ttotal > 0x80000000ull) { c->err = what + capped; return done(MT_E_INVALID); }
+    }
+    off[n] = total;
+    if (!total) return done(MT_OK);
+    const uint64_t units = call ? ttotal : total;
+    mt_ctx::DevBuf& arena = call ? c->b_wtext : c->b_xout;
+    if (call && (rc = mtb_ensure(c, c->b_wout, sizeof(mt_walk_rec) * total))) return done(rc);
+    if (units && (rc = mtb_ensure(c, arena, 2ull * units))) return done(rc);
+    if (call) { call->out = (mt_walk_rec*)c->b_wout.p; call->cap = total; }
+    if (units) { c->S.x_out = (uint16_t*)arena.p; c->S.x_cap = units; }
+    for (uint32_t k = 0; k < n; k++) q[k].ref = count_kind - 1;
+    mtb_h2d(c, c->b_q.p, q.data(), sizeof(MtQuery) * n);
+    std::vector<MtRangeQ> y(n);
+    if ((rc = pass(y))) return done(rc);
+    for (uint32_t i = 0; i < n; i++)
+        if (y[i].filled != x[i].count || y[i].tfilled != x[i].tcount) { c->err = what + ": the passes disagree"; return done(MT_E_INVALID); }
+    return done(MT_OK);
+}
+static_assert(MT_QK_TEXT_FILL == MT_QK_TEXT_COUNT - 1 && MT_QK_WALK_FILL == MT_QK_WALK_COUNT - 1, "a fill kind lies below its count kind");
+
+// Text ranges: the text comes down once.
 int MT_FN(get_text_range)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t* start, const int32_t* end,
                           const int32_t* ref, const int32_t* cli, const uint16_t* placeholder, uint32_t placeholder_len,
                           const uint16_t** arena, const uint64_t** off) {
@@ -1341,61 +1401,24 @@ int MT_FN(get_text_range)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int
     c->range_arena.clear();
     *arena = c->range_arena.data(); *off = c->range_off.data();
     if (n == 0) return MT_OK;
-    if (n > 0x7FFFFFFFu) { c->err = "text range: too many queries"; return MT_E_INVALID; }
-    std::vector<MtTextQ> x(n);
-    for (uint32_t i = 0; i < n; i++) {
-        x[i].start = start ? start[i] : 0; x[i].end = end ? end[i] : MT_POS_UNDEFINED;
-        x[i].ref = (ref && ref[i] >= 0) ? ref[i] : -1; x[i].client = cli ? cli[i] : -1;
-        x[i].at = 0; x[i].count = 0; x[i].filled = 0; x[i].pad = 0;
-    }
-    std::vector<uint32_t> ord;
-    std::vector<MtQuery> q;
-    uint32_t ng = 0;
-    int rc;
-    if ((rc = mt_stage_queries(c, n, docs, nullptr, nullptr, nullptr, MT_QK_TEXT_COUNT, ord, q, ng))) return rc;
-    if ((rc = mtb_ensure(c, c->b_xq, sizeof(MtTextQ) * n))) return rc;
-    mtb_h2d(c, c->b_xq.p, x.data(), sizeof(MtTextQ) * n);
-    c->S.x_q = (MtTextQ*)c->b_xq.p; c->S.x_nq = n; c->S.x_phlen = placeholder_len;
+    c->S.x_phlen = placeholder_len;
     for (uint32_t k = 0; k < MT_TEXT_PLACEHOLDER_MAX / 2; k++) {
         const uint32_t a = 2 * k < placeholder_len ? placeholder[2 * k] : 0u, b = 2 * k + 1 < placeholder_len ? placeholder[2 * k + 1] : 0u;
         c->S.x_ph[k] = a | (b << 16);
     }
-    c->S.x_out = nullptr; c->S.x_cap = 0;
-    auto done = [&](int r) { c->S.x_q = nullptr; c->S.x_nq = 0; c->S.x_out = nullptr; c->S.x_cap = 0; return r; };
-    if ((rc = mtb_launch_query(c, (const MtQuery*)c->b_q.p, (const uint32_t*)c->b_qgrp.p, (MtQueryOut*)c->b_qout.p, ng))) return done(rc);
-    if ((rc = mtb_sync(c))) return done(rc);
-    mtb_d2h(c, x.data(), c->b_xq.p, sizeof(MtTextQ) * n);
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        x[i].at = total; c->range_off[i] = total;
-        total += x[i].count;
-        if (total > 0x80000000ull) { c->err = "text range: the answers hold more than 2^31 units; split the call"; return done(MT_E_INVALID); }
-    }
-    c->range_off[n] = total;
-    if (total) {
-        if ((rc = mtb_ensure(c, c->b_xout, 2ull * total))) return done(rc);
-        mtb_h2d(c, c->b_xq.p, x.data(), sizeof(MtTextQ) * n);
-        for (uint32_t k = 0; k < n; k++) q[k].ref = MT_QK_TEXT_FILL;
-        mtb_h2d(c, c->b_q.p, q.data(), sizeof(MtQuery) * n);
-        c->S.x_out = (uint16_t*)c->b_xout.p; c->S.x_cap = total;
-        if ((rc = mtb_launch_query(c, (const MtQuery*)c->b_q.p, (const uint32_t*)c->b_qgrp.p, (MtQueryOut*)c->b_qout.p, ng))) return done(rc);
-        if ((rc = mtb_sync(c))) return done(rc);
-        std::vector<MtTextQ> y(n);
-        mtb_d2h(c, y.data(), c->b_xq.p, sizeof(MtTextQ) * n);
-        for (uint32_t i = 0; i < n; i++)
-            if (y[i].filled != x[i].count) { c->err = "text range: the passes disagree"; return done(MT_E_INVALID); }
-        c->range_arena.resize((size_t)total);
-        mtb_d2h(c, c->range_arena.data(), c->b_xout.p, 2ull * total);
-    }
+    uint64_t total = 0, ttotal = 0;
+    const int rc = mt_range_passes(c, "text range", ": the answers hold more than 2^31 units; split the call", n, docs, start, end, ref,
+                                   cli, MT_QK_TEXT_COUNT, nullptr, c->range_off.data(), total, ttotal);
+    if (rc) return rc;
+    c->range_arena.resize((size_t)total);
+    if (total) mtb_d2h(c, c->range_arena.data(), c->b_xout.p, 2ull * total);
     *arena = c->range_arena.data(); *off = c->range_off.data();
-    return done(MT_OK);
+    return MT_OK;
 }
 
-// Segment walks (mt_query.h): as text ranges, the records go up once per pass and the fill's carry
-// the offsets the counts gave; the walk's records and text come down once.  Then the distinct
-// (document, prop_set) pairs the records name are fetched by one more launch of the query kernel
-// (MT_QK_PSET copies a map's chunks, packed, into a buffer the call's MtWalkCall names) and written out
-// once each.
+// Segment walks: the walk's records and text come down once.  Then the distinct (document,
+// prop_set) pairs the records name are fetched by one more launch of the query kernel (MT_QK_PSET
+// copies a map's chunks, packed, into a buffer the call's MtWalkCall names) and written out once each.
 int MT_FN(walk_segments)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t* start, const int32_t* end,
                          const int32_t* ref, const int32_t* cli, uint32_t flags, const mt_walk_rec** recs, const uint64_t** rec_off,
                          const uint16_t** text_arena, const mt_walk_maps** maps) {
@@ -1418,65 +1441,21 @@ int MT_FN(walk_segments)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int3
     };
     give();
     if (n == 0) return MT_OK;
-    if (n > 0x7FFFFFFFu) { c->err = "walk: too many queries"; return MT_E_INVALID; }
-    std::vector<MtWalkQ> x(n);
-    for (uint32_t i = 0; i < n; i++) {
-        MtWalkQ& w = x[i];
-        w = MtWalkQ{};
-        w.start = start ? start[i] : 0; w.end = end ? end[i] : MT_POS_UNDEFINED;
-        w.ref = (ref && ref[i] >= 0) ? ref[i] : -1; w.client = cli ? cli[i] : -1;
-        for (const int32_t v : {w.start, w.end})
-            if (v != MT_POS_UNDEFINED && (v < -(1 << 30) || v > (1 << 30))) { c->err = "walk: start / end outside [-2^30, 2^30]"; return MT_E_INVALID; }
-    }
-    std::vector<uint32_t> ord;
-    std::vector<MtQuery> q;
-    uint32_t ng = 0;
-    int rc;
-    if ((rc = mt_stage_queries(c, n, docs, nullptr, nullptr, nullptr, MT_QK_WALK_COUNT, ord, q, ng))) return rc;
-    if ((rc = mtb_ensure(c, c->b_wq, sizeof(MtWalkQ) * n))) return rc;
-    mtb_h2d(c, c->b_wq.p, x.data(), sizeof(MtWalkQ) * n);
-    // the call's state lives in device memory, reached through x_walk (mt_core.h: MtState does not grow)
-    if ((rc = mtb_ensure(c, c->b_wcall, sizeof(MtWalkCall)))) return rc;
-    MtWalkCall call{};
-    call.q = (MtWalkQ*)c->b_wq.p; call.nq = n; call.flags = text ? MT_WALK_TEXT : 0u;
-    mtb_h2d(c, c->b_wcall.p, &call, sizeof call);
-    c->S.x_walk = (const MtWalkCall*)c->b_wcall.p; c->S.x_nq = 0; c->S.x_out = nullptr; c->S.x_cap = 0;
-    auto done = [&](int r) { c->S.x_q = nullptr; c->S.x_nq = 0; c->S.x_out = nullptr; c->S.x_cap = 0; return r; };
-    if ((rc = mtb_launch_query(c, (const MtQuery*)c->b_q.p, (const uint32_t*)c->b_qgrp.p, (MtQueryOut*)c->b_qout.p, ng))) return done(rc);
-    if ((rc = mtb_sync(c))) return done(rc);
-    mtb_d2h(c, x.data(), c->b_wq.p, sizeof(MtWalkQ) * n);
-    uint64_t total = 0, ttotal = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        x[i].at = total; x[i].tat = ttotal; c->walk_off[i] = total;
-        total += x[i].count; ttotal += x[i].tcount;
-        if (total > 0x80000000ull || ttotal > 0x80000000ull) {
-            c->walk_off.assign((size_t)n + 1, 0);
-            c->err = "walk: the answers hold more than 2^31 records or text units; split the call";
-            return done(MT_E_INVALID);
-        }
-    }
-    c->walk_off[n] = total;
-    if (!total) return done(MT_OK);
-    if ((rc = mtb_ensure(c, c->b_wout, sizeof(mt_walk_rec) * total))) return done(rc);
-    if (ttotal && (rc = mtb_ensure(c, c->b_wtext, 2ull * ttotal))) return done(rc);
-    mtb_h2d(c, c->b_wq.p, x.data(), sizeof(MtWalkQ) * n);
-    for (uint32_t k = 0; k < n; k++) q[k].ref = MT_QK_WALK_FILL;
-    mtb_h2d(c, c->b_q.p, q.data(), sizeof(MtQuery) * n);
-    call.out = (mt_walk_rec*)c->b_wout.p; call.cap = total;
-    mtb_h2d(c, c->b_wcall.p, &call, sizeof call);
-    if (ttotal) { c->S.x_out = (uint16_t*)c->b_wtext.p; c->S.x_cap = ttotal; }
-    auto fail = [&](int r) { c->walk_off.assign((size_t)n + 1, 0); return done(r); };
-    if ((rc = mtb_launch_query(c, (const MtQuery*)c->b_q.p, (const uint32_t*)c->b_qgrp.p, (MtQueryOut*)c->b_qout.p, ng))) return fail(rc);
-    if ((rc = mtb_sync(c))) return fail(rc);
-    std::vector<MtWalkQ> y(n);
-    mtb_d2h(c, y.data(), c->b_wq.p, sizeof(MtWalkQ) * n);
     for (uint32_t i = 0; i < n; i++)
-        if (y[i].filled != x[i].count || y[i].tfilled != x[i].tcount) { c->err = "walk: the passes disagree"; return fail(MT_E_INVALID); }
+        for (const int32_t v : {start ? start[i] : 0, end ? end[i] : 0})
+            if (v != MT_POS_UNDEFINED && (v < -(1 << 30) || v > (1 << 30))) { c->err = "walk: start / end outside [-2^30, 2^30]"; return MT_E_INVALID; }
+    MtWalkCall call{};
+    call.flags = text ? MT_WALK_TEXT : 0u;
+    auto fail = [&](int r) { c->walk_off.assign((size_t)n + 1, 0); return r; };
+    uint64_t total = 0, ttotal = 0;
+    int rc = mt_range_passes(c, "walk", ": the answers hold more than 2^31 records or text units; split the call", n, docs, start, end,
+                             ref, cli, MT_QK_WALK_COUNT, &call, c->walk_off.data(), total, ttotal);
+    if (rc) return fail(rc);
+    if (!total) return MT_OK;
     c->walk_recs.resize((size_t)total);
     mtb_d2h(c, c->walk_recs.data(), c->b_wout.p, sizeof(mt_walk_rec) * total);
     c->walk_arena.resize((size_t)ttotal);
     if (ttotal) mtb_d2h(c, c->walk_arena.data(), c->b_wtext.p, 2ull * ttotal);
-    done(MT_OK);
     // the distinct maps, in the order the records first name them; the fill left each map's key
     // count in the record's `map`, which places the maps' chunks
     std::unordered_map<uint64_t, int32_t> seen;
@@ -1500,6 +1479,9 @@ int MT_FN(walk_segments)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int3
         }
     if (!c->walk_map_doc.empty()) {
         const uint32_t m = (uint32_t)c->walk_map_doc.size();
+        std::vector<uint32_t> ord;
+        std::vector<MtQuery> q;
+        uint32_t ng = 0;
         if ((rc = mt_stage_queries(c, m, c->walk_map_doc.data(), mpos.data(), nullptr, mat.data(), MT_QK_PSET, ord, q, ng))) return fail(rc);
         if ((rc = mtb_ensure(c, c->b_wmaps, sizeof(MtPSet) * chunks))) return fail(rc);
         call.out = nullptr; call.cap = 0; call.maps = (MtPSet*)c->b_wmaps.p; call.mcap = chunks;

@@ -315,15 +315,16 @@ struct MtState {                              // device pools, doc-major
     // index's record array (t_cap records)
     const uint8_t* t_match; uint32_t t_key, t_nvalues;
     mt_tile_rec* t_out; unsigned long long t_cap;
-    // text ranges (mt_query.h; set per call by mt_get_text_range): the call's query records
-    // (MtQuery::pos indexes them), the placeholder a marker stands for (x_phlen <= 16 UTF-16
-    // units, two a word) and the fill pass's output arena (x_cap units)
+    // the range queries (mt_query.h: two visitors of one scan; set per call, by one two-pass driver
+    // that also clears what it set, mt_api_impl.h).  A text range (mt_get_text_range): the call's
+    // query records (MtRangeQ; MtQuery::pos indexes them), the placeholder a marker stands for
+    // (x_phlen <= 16 UTF-16 units, two a word) and the fill pass's output arena (x_cap units).
     // A segment walk (mt_walk_segments) adds nothing here: MtState is an argument of every kernel,
     // the replay kernels included, and does not grow for a cold path.  A walk's state lives in a
     // MtWalkCall in device memory, and during its launches this one pointer names it as x_walk,
     // with x_nq == 0, so a text kind finds no record; x_out / x_cap are then the walk's text arena.
     // Only one of the two calls is under way at a time, and each clears the pointer when it ends.
-    union { struct MtTextQ* x_q; const struct MtWalkCall* x_walk; };
+    union { struct MtRangeQ* x_q; const struct MtWalkCall* x_walk; };
     uint32_t x_nq, x_phlen;
     uint32_t x_ph[MT_TEXT_PLACEHOLDER_MAX / 2];
     uint16_t* x_out; unsigned long long x_cap;
@@ -332,21 +333,16 @@ struct MtState {                              // device pools, doc-major
 // fill pass's record array (cap records), and where MT_QK_PSET copies the distinct property maps,
 // chunk by chunk (mcap chunks).
 struct __attribute__((aligned(16))) MtWalkCall {
-    struct MtWalkQ* q; uint32_t nq, flags;
+    struct MtRangeQ* q; uint32_t nq, flags;
     mt_walk_rec* out; unsigned long long cap;
     MtPSet* maps; unsigned long long mcap;
 };
-// One segment walk: the range and the view as the caller gave them, where its records and its
-// text go, what the count pass found and what the fill pass wrote.
-struct __attribute__((aligned(16))) MtWalkQ {
+// One range query, a text range or a segment walk: the range and the view as the caller gave them,
+// where the answer goes (a text range's units, a walk's records), what the count pass found and
+// what the fill pass wrote; the same three for a walk's text, which a text range leaves zero.
+struct __attribute__((aligned(16))) MtRangeQ {
     int32_t start, end, ref, client;
     unsigned long long at, count, filled, tat, tcount, tfilled;
-};
-// One text-range query: the range and the view as the caller gave them, where the answer goes
-// in the arena, the units the count pass found and those the fill pass wrote.
-struct __attribute__((aligned(16))) MtTextQ {
-    int32_t start, end, ref, client;
-    unsigned long long at, count, filled, pad;
 };
 #define MT_VINFO_ID    0x3FFFFFFF
 #define MT_VINFO_NONE  0x3FFFFFFF

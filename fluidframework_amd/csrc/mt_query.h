@@ -5,11 +5,13 @@
 // and tile search (mt_find_tile, mt_tile_index) over a document-order scan of the rows:
 //   MergeTree.findTile                    MT/mergeTree.ts:1752-1778 (search :1780-1820,
 //                                         backwardSearch :1822-1866; the rule: include/mtgpu.h)
-// and text ranges under any view (mt_get_text_range) over the same scan:
+// and the range queries, two visitors of one scan of a range under any view (MtViewScan: enter,
+// load a unit, advance; mt_scan_copy places a unit's text), which runs on the same cursor:
 //   MergeTreeTextHelper.getText           MT/textSegment.ts:163-194 (gatherText :196-284, over
-//                                         mapRange -> nodeMap MT/mergeTree.ts:2927-2994)
-// and segment walks under any view (mt_walk_segments), a record per visited row, over it too:
-//   Client.walkSegments                   MT/client.ts:282-295 (mapRange -> nodeMap, as above)
+//                                         mapRange -> nodeMap MT/mergeTree.ts:2927-2994):
+//                                         mt_get_text_range, each row's clip to the range
+//   Client.walkSegments                   MT/client.ts:282-295 (mapRange -> nodeMap, as above):
+//                                         mt_walk_segments, a record per visited row
 // Batched: the host groups the queries by document, one wave takes a document's queries
 // in order (the perspective's U set is reused while consecutive queries share it).  A
 // query reads the document and writes only the wave's U scratch of that document; a tile
@@ -25,8 +27,8 @@
 #define MT_QK_TILE (-2)
 #define MT_QK_TILE_COUNT (-3)
 #define MT_QK_TILE_FILL (-4)
-// a text range (mt_get_text_range): pos is the query's record in MtState::x_q, which holds the
-// range and the view; the count pass and the fill pass of the same scan
+// a text range (mt_get_text_range): pos is the query's record (MtRangeQ) in MtState::x_q, which
+// holds the range and the view; the count pass and the fill pass of the same scan
 #define MT_QK_TEXT_COUNT (-5)
 #define MT_QK_TEXT_FILL (-6)
 // a segment walk (mt_walk_segments): pos is the query's record in the call's MtWalkCall, which
@@ -76,6 +78,22 @@ struct MtTileUnit {
 enum { MT_TD_POS = 0, MT_TD_FIRST_VIS, MT_TD_LAST_VIS, MT_TD_FIRST, MT_TD_LAST, MT_TD_PATH };
 
 template <class Eng> MT_HD bool mt_tile_blk_ok(const Eng& e, int b) { return b >= 0 && b < e.blkTop; }
+// Block B's children: the child count clamped to a block's room, the child ids, their observer
+// lengths (0 for an id outside the document's blocks) and the lengths' exclusive scan.
+template <class Eng>
+MT_HD int mt_tile_children(Eng& e, int B, LaneArr<int>& ch, LaneArr<int>& lens, LaneArr<int>& pre) {
+    BlkH h;
+    ch = e.blkLoad(B, h);
+    const int n = h.n < 0 ? 0 : (h.n > MT_MAXN ? MT_MAXN : h.n);
+    const int top = e.blkTop;
+    lens = wave_map(n, [&](int j) MT_LAM {
+        const int b = own(ch, j);
+        const bool ok = (b >= 0) & (b < top);
+        return ok ? e.bk(ok ? b : 0).len : 0;
+    });
+    pre = wave_excl_scan8(lens);
+    return n;
+}
 
 // Down from block B (observer start `base`) to a unit: at each level the child holding
 // observer position P (MT_TD_POS; P < the block's length), the first / last child of non-zero
@@ -87,16 +105,8 @@ MT_HD bool mt_tile_down(Eng& e, MtTileCursor& c, int B, int base, int P, int mod
         if (!mt_tile_blk_ok(e, B)) { c.U = -1; return false; }
         if (uni(e.bk(B).height) <= 1) { c.U = B; c.base = base; return true; }
         if (c.lvl >= MT_MAXH + 1) { c.U = -1; return false; }
-        BlkH h;
-        const auto ch = e.blkLoad(B, h);
-        const int n = h.n < 0 ? 0 : (h.n > MT_MAXN ? MT_MAXN : h.n);
-        const int top = e.blkTop;
-        const auto lens = wave_map(n, [&](int j) MT_LAM {
-            const int b = own(ch, j);
-            const bool ok = (b >= 0) & (b < top);
-            return ok ? e.bk(ok ? b : 0).len : 0;
-        });
-        const auto pre = wave_excl_scan8(lens);
+        LaneArr<int> ch, lens, pre;
+        const int n = mt_tile_children(e, B, ch, lens, pre);
         int j;
         if (mode == MT_TD_POS) {
             const int p = P - base;
@@ -122,16 +132,8 @@ MT_HD bool mt_tile_next(Eng& e, MtTileCursor& c, int dir, bool all) {
     while (c.lvl > 0) {
         const int l = c.lvl - 1;
         const int B = uni(e.sc->pathB[l]), j = uni(e.sc->pathJ[l]), base = uni(e.sc->pathOff[l]);
-        BlkH h;
-        const auto ch = e.blkLoad(B, h);
-        const int n = h.n < 0 ? 0 : (h.n > MT_MAXN ? MT_MAXN : h.n);
-        const int top = e.blkTop;
-        const auto lens = wave_map(n, [&](int k) MT_LAM {
-            const int b = own(ch, k);
-            const bool ok = (b >= 0) & (b < top);
-            return ok ? e.bk(ok ? b : 0).len : 0;
-        });
-        const auto pre = wave_excl_scan8(lens);
+        LaneArr<int> ch, lens, pre;
+        const int n = mt_tile_children(e, B, ch, lens, pre);
         const uint64_t m = wave_ballot(wave_map(n, [&](int k) MT_LAM {
             return (((dir > 0) ? (k > j) : (k < j)) & ((own(lens, k) > 0) | all)) != 0;
         }));
@@ -169,20 +171,21 @@ MT_HD LaneArr<int> mt_tile_unit_rows(Eng& e, const MtTileCursor& c, int& height,
         return (ok & ((t & 7) < e.bk(bb).n) & (g >= 0) & (g < rtop)) ? g : -1;
     });
 }
-// Loads the cursor's unit: the row ids, then the row's first two quads (len seq rseq meta |
-// toff props parent tcap), as scourLeaves does.
+// Quad k of each row of a unit (len seq rseq meta | toff props parent tcap | ovl rcl mid), zero
+// where the lane holds no row; lanes [0, span).
+template <class Eng>
+MT_HD LaneArr<MtQ16a> mt_unit_quad(Eng& e, const LaneArr<int>& row, int span, int k) {
+    return wave_map(span, [&](int t) MT_LAM {
+        const int g = own(row, t);
+        return g >= 0 ? ((const MtQ16a*)&e.row(g))[k] : MtQ16a{0u, 0u, 0u, 0u};
+    });
+}
+// Loads the cursor's unit: the row ids, then the row's first two quads, as scourLeaves does.
 template <class Eng>
 MT_HD void mt_tile_unit(Eng& e, const MtTileCursor& c, MtTileUnit& u) {
     int span = 0;
     u.row = mt_tile_unit_rows(e, c, u.height, span);
-    const auto q0 = wave_map(span, [&](int t) MT_LAM {
-        const int g = own(u.row, t);
-        return g >= 0 ? ((const MtQ16a*)&e.row(g))[0] : MtQ16a{0u, 0u, 0u, 0u};
-    });
-    const auto q1 = wave_map(span, [&](int t) MT_LAM {
-        const int g = own(u.row, t);
-        return g >= 0 ? ((const MtQ16a*)&e.row(g))[1] : MtQ16a{0u, 0u, 0u, 0u};
-    });
+    const auto q0 = mt_unit_quad(e, u.row, span, 0), q1 = mt_unit_quad(e, u.row, span, 1);
     u.len = wave_map(span, [&](int t) MT_LAM { return (int)own(q0, t).x; });
     u.seq = wave_map(span, [&](int t) MT_LAM { return (int)own(q0, t).y; });
     u.rseq = wave_map(span, [&](int t) MT_LAM { return (int)own(q0, t).z; });
@@ -234,6 +237,18 @@ MT_HD bool mt_tile_map_has(Eng& e, const MtState& S, int ps, int lab, MtTileMemo
     return res;
 }
 
+// The nch chunks of property map ps to `to`, one dword per lane (28 dwords a chunk).  The caller
+// has checked that the chunks lie in the document's maps and fit at `to`.
+template <class Eng>
+MT_HD void mt_copy_pset(Eng& e, MtPSet* to, int ps, int nch) {
+    constexpr int W = (int)(sizeof(MtPSet) / 4);
+    for (int base = 0; base < nch * W; base += MT_WAVE) {
+        const int m = (nch * W - base) < MT_WAVE ? (nch * W - base) : MT_WAVE;
+        wave_for(m, [&](int k) MT_LAM { ((int*)to)[base + k] = ((const int*)(e.pset + ps))[base + k]; });
+    }
+    wave_sync();
+}
+
 // One answer record (the 16 dwords of mt_seg_info, the row's text, its map's chunks): row s
 // found at `off` into it with observer start op; s < 0: not found, `resolved` as given.
 template <class Eng>
@@ -264,13 +279,7 @@ MT_HD void mt_query_emit(Eng& e, const MtState& S, MtQueryOut& o, int s, int off
     const auto fv = wave_map(16, [&](int k) MT_LAM { return pick16(f, k); });
     wave_for(16, [&](int k) MT_LAM { ((int*)&o.info)[k] = own(fv, k); });
     wave_for(1, [&](int) MT_LAM { o.text_at = tat; o.pad = 0; });
-    // the property map's chunks, one dword per lane (28 dwords a chunk)
-    constexpr int W = (int)(sizeof(MtPSet) / 4);
-    for (int base = 0; base < nch * W; base += MT_WAVE) {
-        const int m = (nch * W - base) < MT_WAVE ? (nch * W - base) : MT_WAVE;
-        wave_for(m, [&](int k) MT_LAM { ((int*)o.ps)[base + k] = ((const int*)(e.pset + ps))[base + k]; });
-    }
-    wave_sync();
+    mt_copy_pset(e, o.ps, ps, nch);
 }
 
 // The tree path of lane t of the cursor's unit, root first, 3 bits a level (as containing's).
@@ -371,15 +380,131 @@ MT_HD int mt_tile_index_doc(Eng& e, const MtState& S, int lab, MtTileMemo& memo,
     }
 }
 
+/* ------------------------------------------------------------- range scan -- */
+// The rows of a range [lo, end) of a view, in document order, a unit at a time: the one scan under
+// mt_get_text_range and mt_walk_segments, which differ in what they do with a unit's rows.  A
+// unit's rows are lane data: each row's length under the view (vis_rc, branch-free per lane,
+// DESIGN.md §4) and the exclusive scan that places it in the view.
+// The view of a query's (ref, client): true for the local one, every sequenced op applied
+// (removals included), as (refSeq = max, a client id no row carries) sees it.
+MT_INLINE bool mt_view_of(int ref, int qc, int& r, int& c) {
+    const bool local = ref < 0;
+    r = local ? 0x7FFFFFFF : ref;
+    c = (local || qc < 0 || qc >= MT_NONCOLLAB) ? MT_NOBODY : qc;
+    return local;
+}
+struct MtViewScan {
+    MtTileCursor cur;
+    bool local;
+    int r, c;            // the view
+    int pos;             // the view position the cursor's unit starts at
+    int s0;              // remote, until the first unit is loaded: the row containing() found (pos: that row's start)
+};
+struct MtScanUnit {
+    LaneArr<int> row, vl, pre;       // row ids (-1: none), lengths under the view, their exclusive scan
+    LaneArr<MtQ16a> q0, q1, q2;      // the rows' quads (mt_unit_quad); q2 zero where it was not asked for
+    int span, vsum;                  // lanes, and the unit's length under the view
+    int ub, ob;                      // the unit's start in the view, and in the observer's (the cursor's base)
+};
+// Puts the cursor on the unit holding view position lo.  False: the view holds no such position.
+template <class Eng>
+MT_HD bool mt_scan_enter(Eng& e, MtViewScan& s, bool local, int r, int c, int lo) {
+    s.cur.U = -1; s.cur.lvl = 0; s.cur.base = 0;
+    s.local = local; s.r = r; s.c = c; s.pos = 0; s.s0 = -1;
+    if (local) {
+        // the observer's lengths are the view's: subtrees of length 0 hold nothing
+        if (lo >= uni(e.bk(e.root).len)) return false;
+        if (!mt_tile_down(e, s.cur, e.root, 0, lo, MT_TD_POS)) return false;
+        s.pos = s.cur.base;
+        return true;
+    }
+    // one descent under the view (it computes U once); the cursor is rebuilt from its path
+    int off = 0, depth = 0;
+    unsigned long long path = 0;
+    s.s0 = e.containing(lo, r, c, off, depth, path);
+    s.pos = lo - off;
+    return s.s0 >= 0 && mt_tile_down(e, s.cur, e.root, 0, 0, MT_TD_PATH, path, depth);
+}
+// Loads the cursor's unit.  The third quad is read for a remote view (vis_rc needs it) or where
+// the caller asks for it.  False: the first unit does not hold the row containing() found.
+template <class Eng>
+MT_HD bool mt_scan_unit(Eng& e, MtViewScan& s, MtScanUnit& u, bool third) {
+    int height = 0;
+    u.row = mt_tile_unit_rows(e, s.cur, height, u.span);
+    const int span = u.span, r = s.r, c = s.c;
+    const bool local = s.local;
+    u.q0 = mt_unit_quad(e, u.row, span, 0);
+    u.q1 = mt_unit_quad(e, u.row, span, 1);
+    u.q2 = mt_unit_quad(e, u.row, (third || !local) ? span : 0, 2);
+    u.vl = wave_map(span, [&](int t) MT_LAM {
+        const MtQ16a a = own(u.q0, t), x = own(u.q2, t);
+        const int g = own(u.row, t), l = (int)a.x;
+        const unsigned long long ovl = (unsigned long long)x.x | ((unsigned long long)x.y << 32);
+        const bool vis = local ? (a.w & MT_M_REMOVED) == 0 : vis_rc((int)a.y, a.w, (int)a.z, x.z, ovl, r, c, e.ovx, e.ovxN, g);
+        return ((g >= 0) & vis & (l > 0)) ? l : 0;
+    });
+    u.pre = wave_excl_scan(u.vl);
+    u.vsum = wave_sum(u.vl);
+    if (s.s0 >= 0) {                                // the first unit's start under the view, from the row containing() found
+        const int s0 = s.s0;
+        const int t0 = wave_first(wave_map(span, [&](int t) MT_LAM { return own(u.row, t) == s0; }));
+        if (t0 < 0) return false;
+        s.pos -= wave_at(u.pre, t0);
+        s.s0 = -1;
+    }
+    u.ub = s.pos; u.ob = s.cur.base;
+    return true;
+}
+// Past a unit of length vsum under the view.  False: the view position reached `end`, or no unit follows.
+template <class Eng>
+MT_HD bool mt_scan_next(Eng& e, MtViewScan& s, int vsum, int end) {
+    s.pos += vsum;
+    if (s.pos >= end) return false;
+    if (!mt_tile_next(e, s.cur, 1, !s.local)) return false;     // remote: a row the observer removed may be visible
+    if (s.local) s.pos = s.cur.base;
+    return true;
+}
+// A unit's output: row t gives olen[t] UTF-16 units (opre: their exclusive scan, T: their sum),
+// the document's text from index src[t] on, or for src[t] == -1 the placeholder in the words phw.
+// One lane per *output* unit in rounds of 64: the lane finds its row by a binary search of the
+// inclusive output scan (kept in the wave's scratch), so the stores are contiguous and one long
+// row costs what many short ones do.  Units go to out[at .. at + T), as far as `room` reaches.
+template <class Eng>
+MT_HD void mt_scan_copy(Eng& e, const LaneArr<int>& olen, const LaneArr<int>& opre, int T, const LaneArr<int>& src,
+                        const int* phw, uint16_t* out, unsigned long long at, unsigned long long room) {
+    const int ttop = e.textTop;
+    wave_for(MT_WAVE, [&](int t) MT_LAM {
+        e.sc->hold[t] = own(opre, t) + own(olen, t);
+        e.sc->holdLen[t] = own(src, t);
+    });
+    wave_sync();
+    for (int base = 0; base < T; base += MT_WAVE) {
+        const int m = (T - base) < MT_WAVE ? (T - base) : MT_WAVE;
+        const unsigned long long d0 = at + (unsigned long long)base;
+        wave_for(m, [&](int k) MT_LAM {
+            const int j = base + k;
+            int t = 0;                              // the first row whose inclusive end passes j
+            for (int step = 32; step; step >>= 1) t += (e.sc->hold[t + step - 1] <= j) ? step : 0;
+            const int before = e.sc->hold[t ? t - 1 : 0];
+            const int kk = j - (t ? before : 0), sx = e.sc->holdLen[t];
+            // the text index clamped to the live half's top; stores bounded by the answer's room
+            int ti = sx + kk;
+            ti = ti >= ttop ? ttop - 1 : ti;
+            ti = ti < 0 ? 0 : ti;
+            const bool tx = ((sx >= 0) & (ttop > 0)) != 0;
+            const uint32_t w = (uint32_t)pick8(phw, (kk >> 1) & 7);
+            const uint16_t v = tx ? e.text[ti] : (uint16_t)((kk & 1) ? (w >> 16) : (w & 0xFFFFu));
+            if (d0 + (unsigned long long)k < room) out[d0 + (unsigned long long)k] = v;
+        });
+    }
+    wave_sync();
+}
+
 /* ------------------------------------------------------------ text ranges -- */
 // getText(refSeq, clientId, placeholder, start, end) of one document (the rule: include/mtgpu.h)
-// as one document-order scan from the unit holding the range's start.  A unit's rows are lane
-// data: each row's length under the view (vis_rc, branch-free per lane), the
-// exclusive scan that places it in the view, its clip to the range, and a second scan over the
-// output lengths.  The fill then runs one lane per *output* unit in rounds of 64: the lane finds
-// its row by a binary search of the output scan (kept in the wave's scratch), so the stores are
-// contiguous and one long row costs what many short ones do.  out null: count only.  Returns
-// the answer's length; units go to out[0 .. length), as far as `room` reaches.
+// as a visitor of the range scan, entered at the unit holding the range's start: each row's clip
+// to the range and a second scan over the output lengths.  out null: count only.  Returns the
+// answer's length; units go to out[0 .. length), as far as `room` reaches.
 template <class Eng>
 MT_HD unsigned long long mt_text_range_doc(Eng& e, const MtState& S, int start, int end, int ref, int qc, uint16_t* out,
                                            unsigned long long room) {
@@ -390,64 +515,21 @@ MT_HD unsigned long long mt_text_range_doc(Eng& e, const MtState& S, int start, 
     const bool swapped = start > E;
     const int lo = swapped ? E : (start < 0 ? 0 : start), hi = swapped ? start : E;
     if (swapped ? lo <= 0 : hi <= lo) return 0;
-    const bool local = ref < 0;
-    const int r = local ? 0x7FFFFFFF : ref, c = (local || qc < 0 || qc >= MT_NONCOLLAB) ? MT_NOBODY : qc;
+    int r, c;
+    const bool local = mt_view_of(ref, qc, r, c);
     const int plen = S.x_phlen > MT_TEXT_PLACEHOLDER_MAX ? MT_TEXT_PLACEHOLDER_MAX : (int)S.x_phlen;
     static_assert(MT_TEXT_PLACEHOLDER_MAX == 16, "the placeholder is picked from eight words");
-    const int* phw = (const int*)S.x_ph;            // read by constant index only (pick8)
-    MtTileCursor cur; cur.U = -1; cur.lvl = 0; cur.base = 0;
-    int ubase = 0, s0 = -1, off0 = 0;
-    if (local) {
-        // the observer's lengths are the view's: subtrees of length 0 hold nothing
-        if (lo >= uni(e.bk(e.root).len)) return 0;
-        if (!mt_tile_down(e, cur, e.root, 0, lo, MT_TD_POS)) return 0;
-        ubase = cur.base;
-    } else {
-        // one descent under the view (it computes U once); the cursor is rebuilt from its path
-        int depth = 0;
-        unsigned long long path = 0;
-        s0 = e.containing(lo, r, c, off0, depth, path);
-        if (s0 < 0) return 0;
-        if (!mt_tile_down(e, cur, e.root, 0, 0, MT_TD_PATH, path, depth)) return 0;
-    }
+    MtViewScan sc;
+    MtScanUnit u;
+    if (!mt_scan_enter(e, sc, local, r, c, lo)) return 0;
     unsigned long long done = 0;
-    const int ttop = e.textTop;
-    for (bool first = true;; first = false) {
-        int height = 0, span = 0;
-        const auto row = mt_tile_unit_rows(e, cur, height, span);
-        // len seq rseq meta | toff props parent tcap | ovl rcl mid (the third for a remote view only)
-        const auto q0 = wave_map(span, [&](int t) MT_LAM {
-            const int g = own(row, t);
-            return g >= 0 ? ((const MtQ16a*)&e.row(g))[0] : MtQ16a{0u, 0u, 0u, 0u};
-        });
-        const auto q1 = wave_map(span, [&](int t) MT_LAM {
-            const int g = own(row, t);
-            return g >= 0 ? ((const MtQ16a*)&e.row(g))[1] : MtQ16a{0u, 0u, 0u, 0u};
-        });
-        const auto q2 = wave_map(local ? 0 : span, [&](int t) MT_LAM {
-            const int g = own(row, t);
-            return g >= 0 ? ((const MtQ16a*)&e.row(g))[2] : MtQ16a{0u, 0u, 0u, 0u};
-        });
-        const auto vl = wave_map(span, [&](int t) MT_LAM {
-            const MtQ16a a = own(q0, t), x = own(q2, t);
-            const int g = own(row, t), l = (int)a.x;
-            const unsigned long long ovl = (unsigned long long)x.x | ((unsigned long long)x.y << 32);
-            const bool vis = local ? (a.w & MT_M_REMOVED) == 0 : vis_rc((int)a.y, a.w, (int)a.z, x.z, ovl, r, c, e.ovx, e.ovxN, g);
-            return ((g >= 0) & vis & (l > 0)) ? l : 0;
-        });
-        const auto pre = wave_excl_scan(vl);
-        const int vsum = wave_sum(vl);
-        if (first && !local) {                      // the unit's start under the view, from the row containing() found
-            const int s = s0;
-            const int t0 = wave_first(wave_map(span, [&](int t) MT_LAM { return own(row, t) == s; }));
-            if (t0 < 0) return 0;
-            ubase = lo - off0 - wave_at(pre, t0);
-        }
-        const int ub = ubase;
+    do {
+        if (!mt_scan_unit(e, sc, u, false)) return 0;
+        const int ub = u.ub;
         // output units per row: the clip of [p, p + l) to [lo, hi); a marker 0 or the placeholder
-        const auto olen = wave_map(span, [&](int t) MT_LAM {
-            const int p = ub + own(pre, t), l = own(vl, t);
-            const bool marker = (own(q0, t).w & MT_M_MARKER) != 0;
+        const auto olen = wave_map(u.span, [&](int t) MT_LAM {
+            const int p = ub + own(u.pre, t), l = own(u.vl, t);
+            const bool marker = (own(u.q0, t).w & MT_M_MARKER) != 0;
             const int a = lo > p ? lo : p, b = hi < p + l ? hi : p + l;
             const bool one = ((p < lo) & (hi < p + l) & !marker) != 0;
             const int n = swapped ? (one ? hi - lo : 0) : (b > a ? b - a : 0);
@@ -456,132 +538,64 @@ MT_HD unsigned long long mt_text_range_doc(Eng& e, const MtState& S, int start, 
         const auto opre = wave_excl_scan(olen);
         const int T = wave_sum(olen);
         if (out && T > 0) {
-            // the output scan (inclusive) and each row's first source unit (-1: the placeholder)
-            wave_for(MT_WAVE, [&](int t) MT_LAM {
-                const int p = ub + own(pre, t);
-                const bool marker = (own(q0, t).w & MT_M_MARKER) != 0;
-                e.sc->hold[t] = own(opre, t) + own(olen, t);
-                e.sc->holdLen[t] = marker ? -1 : (int)own(q1, t).x + ((lo > p ? lo : p) - p);
+            // each row's first source unit (-1: the placeholder)
+            const auto src = wave_map(MT_WAVE, [&](int t) MT_LAM {
+                const int p = ub + own(u.pre, t);
+                const bool marker = (own(u.q0, t).w & MT_M_MARKER) != 0;
+                return marker ? -1 : (int)own(u.q1, t).x + ((lo > p ? lo : p) - p);
             });
-            wave_sync();
-            for (int base = 0; base < T; base += MT_WAVE) {
-                const int m = (T - base) < MT_WAVE ? (T - base) : MT_WAVE;
-                const unsigned long long d0 = done + (unsigned long long)base;
-                wave_for(m, [&](int k) MT_LAM {
-                    const int j = base + k;
-                    int t = 0;                      // the first row whose inclusive end passes j
-                    for (int step = 32; step; step >>= 1) t += (e.sc->hold[t + step - 1] <= j) ? step : 0;
-                    const int before = e.sc->hold[t ? t - 1 : 0];
-                    const int kk = j - (t ? before : 0), sx = e.sc->holdLen[t];
-                    // the text index clamped to the live half's top; stores bounded by the record's room
-                    int ti = sx + kk;
-                    ti = ti >= ttop ? ttop - 1 : ti;
-                    ti = ti < 0 ? 0 : ti;
-                    const bool tx = ((sx >= 0) & (ttop > 0)) != 0;
-                    const uint32_t w = (uint32_t)pick8(phw, (kk >> 1) & 7);
-                    const uint16_t v = tx ? e.text[ti] : (uint16_t)((kk & 1) ? (w >> 16) : (w & 0xFFFFu));
-                    if (d0 + (unsigned long long)k < room) out[d0 + (unsigned long long)k] = v;
-                });
-            }
-            wave_sync();
+            mt_scan_copy(e, olen, opre, T, src, (const int*)S.x_ph, out, done, room);
         }
         done += (unsigned long long)T;
-        if (swapped) break;
-        ubase += vsum;
-        if (ubase >= hi) break;                     // the running view position reached E
-        if (!mt_tile_next(e, cur, 1, !local)) break;    // remote: a row the observer removed may be visible
-        if (local) ubase = cur.base;
-    }
+    } while (!swapped && mt_scan_next(e, sc, u.vsum, hi));
     return done;
 }
 
 /* ---------------------------------------------------------- segment walks -- */
-// walkSegments(handler, start, end) of one document under a view (the rule: include/mtgpu.h): the
-// scan of mt_text_range_doc, entered the same way, with nodeMap's visit test (:2964) as lane
-// data: E - p > 0 && l > 0 && S - p < l, p from the exclusive scan of the lengths under the
+// walkSegments(handler, start, end) of one document under a view (the rule: include/mtgpu.h), a
+// visitor of the range scan with nodeMap's visit test (:2964) as lane data:
+// E - p > 0 && l > 0 && S - p < l, p from the exclusive scan of the lengths under the
 // view.  For S < E the first visited row holds max(S, 0) and the scan runs until the view
 // position reaches E; for S >= E the one row that can pass holds E, and the scan ends with its
 // unit.  A visited row's record goes to rec[popcount of the visited lanes before it]; its
 // obs_pos is the unit's observer start (the cursor's base, kept by every descent mode) plus the
 // exclusive scan of the observer's lengths, which in the local view is p itself.  With text, the
-// visited text rows' whole texts follow each other in the arena, copied one lane per output unit
-// in rounds of 64 as the text fill does.  rec null: count only.  Returns the records; tcount:
-// the text units.  Stores reach rec[0 .. room) and txt[0 .. troom) only; tat: where txt starts
-// in the call's arena (a record's text_off is absolute).
+// visited text rows' whole texts follow each other in the arena.  rec null: count only.  Returns
+// the records; tcount: the text units.  Stores reach rec[0 .. room) and txt[0 .. troom) only;
+// tat: where txt starts in the call's arena (a record's text_off is absolute).
 template <class Eng>
 MT_HD unsigned long long mt_walk_doc(Eng& e, const MtState& S, int start, int end, int ref, int qc, bool text, mt_walk_rec* rec,
                                      unsigned long long room, uint16_t* txt, unsigned long long tat, unsigned long long troom,
                                      unsigned long long& tcount) {
     tcount = 0;
     if (!mt_tile_blk_ok(e, e.root)) return 0;
-    const bool local = ref < 0;
-    const int r = local ? 0x7FFFFFFF : ref, c = (local || qc < 0 || qc >= MT_NONCOLLAB) ? MT_NOBODY : qc;
+    int r, c;
+    const bool local = mt_view_of(ref, qc, r, c);
     const int Sx = start == (int)0x80000000 ? 0 : start;
     int E = end;
     if (end == (int)0x80000000) E = local ? uni(e.bk(e.root).len) : e.perspectiveLength(r, c);   // undefined: L
     if (E <= 0) return 0;
     const bool one = Sx >= E;                       // at most one row, the one holding E
-    const int lo = one ? E : (Sx < 0 ? 0 : Sx);
-    MtTileCursor cur; cur.U = -1; cur.lvl = 0; cur.base = 0;
-    int ubase = 0, s0 = -1, off0 = 0;
-    if (local) {
-        if (lo >= uni(e.bk(e.root).len)) return 0;
-        if (!mt_tile_down(e, cur, e.root, 0, lo, MT_TD_POS)) return 0;
-        ubase = cur.base;
-    } else {
-        int depth = 0;
-        unsigned long long path = 0;
-        s0 = e.containing(lo, r, c, off0, depth, path);
-        if (s0 < 0) return 0;
-        if (!mt_tile_down(e, cur, e.root, 0, 0, MT_TD_PATH, path, depth)) return 0;
-    }
+    MtViewScan sc;
+    MtScanUnit u;
+    if (!mt_scan_enter(e, sc, local, r, c, one ? E : (Sx < 0 ? 0 : Sx))) return 0;
     unsigned long long done = 0, tdone = 0;
-    const int ttop = e.textTop;
-    for (bool first = true;; first = false) {
-        int height = 0, span = 0;
-        const auto row = mt_tile_unit_rows(e, cur, height, span);
-        // len seq rseq meta | toff props parent tcap | ovl rcl mid
-        const auto q0 = wave_map(span, [&](int t) MT_LAM {
-            const int g = own(row, t);
-            return g >= 0 ? ((const MtQ16a*)&e.row(g))[0] : MtQ16a{0u, 0u, 0u, 0u};
-        });
-        const auto q1 = wave_map(span, [&](int t) MT_LAM {
-            const int g = own(row, t);
-            return g >= 0 ? ((const MtQ16a*)&e.row(g))[1] : MtQ16a{0u, 0u, 0u, 0u};
-        });
-        const auto q2 = wave_map(span, [&](int t) MT_LAM {
-            const int g = own(row, t);
-            return g >= 0 ? ((const MtQ16a*)&e.row(g))[2] : MtQ16a{0u, 0u, 0u, 0u};
-        });
-        const auto vl = wave_map(span, [&](int t) MT_LAM {
-            const MtQ16a a = own(q0, t), x = own(q2, t);
-            const int g = own(row, t), l = (int)a.x;
-            const unsigned long long ovl = (unsigned long long)x.x | ((unsigned long long)x.y << 32);
-            const bool vis = local ? (a.w & MT_M_REMOVED) == 0 : vis_rc((int)a.y, a.w, (int)a.z, x.z, ovl, r, c, e.ovx, e.ovxN, g);
-            return ((g >= 0) & vis & (l > 0)) ? l : 0;
-        });
-        const auto pre = wave_excl_scan(vl);
-        const int vsum = wave_sum(vl);
+    do {
+        if (!mt_scan_unit(e, sc, u, true)) return 0;
+        const int span = u.span, ub = u.ub, ob = u.ob;
         // the observer's lengths: the view's own in the local view
-        const auto opos = local ? pre : wave_excl_scan(wave_map(span, [&](int t) MT_LAM {
-            const MtQ16a a = own(q0, t);
-            return ((own(row, t) >= 0) & ((a.w & MT_M_REMOVED) == 0) & ((int)a.x > 0)) ? (int)a.x : 0;
+        const auto opos = local ? u.pre : wave_excl_scan(wave_map(span, [&](int t) MT_LAM {
+            const MtQ16a a = own(u.q0, t);
+            return ((own(u.row, t) >= 0) & ((a.w & MT_M_REMOVED) == 0) & ((int)a.x > 0)) ? (int)a.x : 0;
         }));
-        if (first && !local) {                      // the unit's start under the view, from the row containing() found
-            const int s = s0;
-            const int t0 = wave_first(wave_map(span, [&](int t) MT_LAM { return own(row, t) == s; }));
-            if (t0 < 0) return 0;
-            ubase = lo - off0 - wave_at(pre, t0);
-        }
-        const int ub = ubase, ob = cur.base;
         const uint64_t hit = wave_ballot(wave_map(span, [&](int t) MT_LAM {
-            const int p = ub + own(pre, t), l = own(vl, t);
+            const int p = ub + own(u.pre, t), l = own(u.vl, t);
             return ((E - p > 0) & (l > 0) & (Sx - p < l)) != 0;     // :2964
         }));
         // text units per visited row: a text row's whole text
         const auto olen = wave_map(span, [&](int t) MT_LAM {
-            const bool marker = (own(q0, t).w & MT_M_MARKER) != 0;
-            return (text & ((hit >> t) & 1ull) & !marker) ? own(vl, t) : 0;
+            const bool marker = (own(u.q0, t).w & MT_M_MARKER) != 0;
+            return (text & ((hit >> t) & 1ull) & !marker) ? own(u.vl, t) : 0;
         });
         const auto opre = wave_excl_scan(olen);
         const int T = wave_sum(olen);
@@ -590,9 +604,9 @@ MT_HD unsigned long long mt_walk_doc(Eng& e, const MtState& S, int start, int en
             wave_for(span, [&](int t) MT_LAM {
                 const unsigned long long k = d0 + (unsigned long long)__builtin_popcountll(hit & ((1ull << t) - 1ull));
                 if (((hit >> t) & 1ull) && k < room) {          // guards the stores only
-                    const MtQ16a a = own(q0, t), b = own(q1, t), x = own(q2, t);
+                    const MtQ16a a = own(u.q0, t), b = own(u.q1, t), x = own(u.q2, t);
                     const bool removed = (a.w & MT_M_REMOVED) != 0, marker = (a.w & MT_M_MARKER) != 0;
-                    const int cl = (int)(a.w & MT_M_CLIENT), p = ub + own(pre, t);
+                    const int cl = (int)(a.w & MT_M_CLIENT), p = ub + own(u.pre, t);
                     mt_walk_rec w;
                     w.pos = p; w.start = Sx - p; w.end = E - p; w.len = (int)a.x;
                     w.seq = (int)a.y; w.client = cl == MT_NONCOLLAB ? -1 : cl;
@@ -602,46 +616,20 @@ MT_HD unsigned long long mt_walk_doc(Eng& e, const MtState& S, int start, int en
                     const int ps = (int)b.y;
                     w.prop_set = ps; w.map = (ps >= 0 && ps < e.psetTop) ? e.pset[ps].n : -1;
                     w.marker_ref_type = marker ? (int)b.x : -1; w.marker_id = (int)x.w - 1;
-                    w.row = own(row, t); w.obs_pos = ob + own(opos, t);
+                    w.row = own(u.row, t); w.obs_pos = ob + own(opos, t);
                     w.text_off = (text && !marker) ? t0 + (unsigned long long)own(opre, t) : 0ull;
                     rec[k] = w;
                 }
             });
         }
         if (txt && T > 0) {
-            // the output scan (inclusive) and each row's first source unit, as the text fill keeps them
-            wave_for(MT_WAVE, [&](int t) MT_LAM {
-                e.sc->hold[t] = own(opre, t) + own(olen, t);
-                e.sc->holdLen[t] = (int)own(q1, t).x;
-            });
-            wave_sync();
-            for (int base = 0; base < T; base += MT_WAVE) {
-                const int m = (T - base) < MT_WAVE ? (T - base) : MT_WAVE;
-                const unsigned long long d0 = tdone + (unsigned long long)base;
-                wave_for(m, [&](int k) MT_LAM {
-                    const int j = base + k;
-                    int t = 0;                      // the first row whose inclusive end passes j
-                    for (int step = 32; step; step >>= 1) t += (e.sc->hold[t + step - 1] <= j) ? step : 0;
-                    const int before = e.sc->hold[t ? t - 1 : 0];
-                    const int kk = j - (t ? before : 0), sx = e.sc->holdLen[t];
-                    // the text index clamped to the live half's top; stores bounded by the query's room
-                    int ti = sx + kk;
-                    ti = ti >= ttop ? ttop - 1 : ti;
-                    ti = ti < 0 ? 0 : ti;
-                    const uint16_t v = ttop > 0 ? e.text[ti] : (uint16_t)0;
-                    if (d0 + (unsigned long long)k < troom) txt[d0 + (unsigned long long)k] = v;
-                });
-            }
-            wave_sync();
+            // each row's first source unit: a visited text row's toff (no row asks for the placeholder)
+            const auto src = wave_map(MT_WAVE, [&](int t) MT_LAM { return (int)own(u.q1, t).x; });
+            mt_scan_copy(e, olen, opre, T, src, (const int*)S.x_ph, txt, tdone, troom);
         }
         done += (unsigned long long)__builtin_popcountll(hit);
         tdone += (unsigned long long)T;
-        if (one) break;
-        ubase += vsum;
-        if (ubase >= E) break;                      // the running view position reached E
-        if (!mt_tile_next(e, cur, 1, !local)) break;    // remote: a row the observer removed may be visible
-        if (local) ubase = cur.base;
-    }
+    } while (!one && mt_scan_next(e, sc, u.vsum, E));
     tcount = tdone;
     return done;
 }
@@ -654,13 +642,7 @@ MT_HD void mt_query_pset(Eng& e, MtPSet* maps, unsigned long long mcap, int ps, 
     n = n < 0 ? 0 : (n > MT_PKEYS ? MT_PKEYS : n);
     const int nch = n > MT_PSK ? (n + MT_PSK - 1) / MT_PSK : 1;
     if (nch > e.psetTop - ps || (unsigned long long)dst + (unsigned long long)nch > mcap) return;
-    constexpr int W = (int)(sizeof(MtPSet) / 4);
-    int* to = (int*)(maps + dst);
-    for (int base = 0; base < nch * W; base += MT_WAVE) {
-        const int m = (nch * W - base) < MT_WAVE ? (nch * W - base) : MT_WAVE;
-        wave_for(m, [&](int k) MT_LAM { to[base + k] = ((const int*)(e.pset + ps))[base + k]; });
-    }
-    wave_sync();
+    mt_copy_pset(e, maps + dst, ps, nch);
 }
 
 template <class Eng>
@@ -676,11 +658,11 @@ MT_HD void mt_query_run(Eng& e, const MtState& S, const MtQuery* q, uint32_t q0,
                 continue;
             }
             const bool fill = ref == MT_QK_WALK_FILL;
-            MtWalkQ* wq = (MtWalkQ*)uni64((unsigned long long)wc->q);
+            MtRangeQ* wq = (MtRangeQ*)uni64((unsigned long long)wc->q);
             mt_walk_rec* wout = (mt_walk_rec*)uni64((unsigned long long)wc->out);
             const unsigned long long wcap = uni64(wc->cap);
             if (!wq || (uint32_t)pos >= uni(wc->nq)) continue;
-            MtWalkQ& x = wq[(uint32_t)pos];
+            MtRangeQ& x = wq[(uint32_t)pos];
             const bool text = (uni(wc->flags) & MT_WALK_TEXT) != 0;
             const unsigned long long at = uni64(x.at), cap = uni64(x.count), tat = uni64(x.tat), tcap = uni64(x.tcount);
             unsigned long long room = (fill && wout && at < wcap) ? wcap - at : 0ull;
@@ -691,7 +673,7 @@ MT_HD void mt_query_run(Eng& e, const MtState& S, const MtQuery* q, uint32_t q0,
             const unsigned long long cnt = mt_walk_doc(e, S, uni(x.start), uni(x.end), uni(x.ref), uni(x.client), text,
                                                        room ? wout + at : nullptr, room, troom ? S.x_out + tat : nullptr, tat,
                                                        troom, tcnt);
-            MtWalkQ* xp = &x;
+            MtRangeQ* xp = &x;
             wave_for(1, [&](int) MT_LAM {
                 if (fill) { xp->filled = cnt; xp->tfilled = tcnt; } else { xp->count = cnt; xp->tcount = tcnt; }
             });
@@ -701,13 +683,13 @@ MT_HD void mt_query_run(Eng& e, const MtState& S, const MtQuery* q, uint32_t q0,
         if (ref <= MT_QK_TEXT_COUNT) {              // a text range: its record holds the query and takes the count
             const bool fill = ref == MT_QK_TEXT_FILL;
             if (!S.x_q || (uint32_t)pos >= S.x_nq) continue;
-            MtTextQ& x = S.x_q[(uint32_t)pos];
+            MtRangeQ& x = S.x_q[(uint32_t)pos];
             const unsigned long long at = uni64(x.at), cap = uni64(x.count);
             unsigned long long room = (fill && S.x_out && at < S.x_cap) ? S.x_cap - at : 0ull;
             room = room < cap ? room : cap;
             const unsigned long long cnt = mt_text_range_doc(e, S, uni(x.start), uni(x.end), uni(x.ref), uni(x.client),
                                                              room ? S.x_out + at : nullptr, room);
-            MtTextQ* xp = &x;
+            MtRangeQ* xp = &x;
             wave_for(1, [&](int) MT_LAM { if (fill) xp->filled = cnt; else xp->count = cnt; });
             wave_sync();
             continue;
@@ -730,10 +712,8 @@ MT_HD void mt_query_run(Eng& e, const MtState& S, const MtQuery* q, uint32_t q0,
             }
             continue;
         }
-        // the local view: every sequenced op applied (removals included), as (refSeq = max,
-        // a client id no row carries) sees it
-        const bool local = ref < 0;
-        const int r = local ? 0x7FFFFFFF : ref, c = (local || qc < 0 || qc >= MT_NONCOLLAB) ? MT_NOBODY : qc;
+        int r, c;
+        mt_view_of(ref, qc, r, c);
         int off = 0, depth = 0;
         unsigned long long path = 0;
         const int s = e.containing(pos, r, c, off, depth, path);

@@ -197,6 +197,11 @@ def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def _ptr(a):
+    """An optional array's address for the ABI: None (a null pointer) when absent or empty."""
+    return a.ctypes.data if a is not None and len(a) else None
+
+
 class Engine:
     """One engine context on one GPU (or, for tests, the host emulation lib)."""
 
@@ -692,13 +697,11 @@ class Engine:
         raw = ctypes.string_at(arena, int(offs[-1]) * 2) if offs[-1] else b""
         return [raw[2 * offs[i]:2 * offs[i + 1]].decode("utf-16-le", "surrogatepass") for i in range(len(d))]
 
-    def get_text_range(self, docs, start=None, end=None, ref_seq=None, client=None, placeholder: str = "") -> list[str]:
-        """mt_get_text_range: MergeTreeTextHelper.getText(ref_seq[i], client[i], placeholder,
-        start[i], end[i]) (MT/textSegment.ts:163-194) of each query, gathered on the device.
-        start / end: None (0 / the view's length) or a sequence whose elements may be None /
-        POS_UNDEFINED for undefined; a scalar is broadcast.  ref_seq None or < 0: the local view.
-        start > end gives what JS substring's swap gives (include/mtgpu.h).  Raw ABI: client is
-        the engine's per-document client index, and "*" is an ordinary one-unit placeholder."""
+    @staticmethod
+    def _range_args(docs, start, end, ref_seq, client):
+        """The arguments the range queries share, as the ABI's arrays: (n, docs, start, end,
+        ref_seq, client), None for an absent one.  start / end: None, or a sequence whose elements
+        may be None / POS_UNDEFINED; scalars are broadcast."""
         d = _u32(docs)
         n = len(d)
 
@@ -706,13 +709,21 @@ class Engine:
             if a is None:
                 return None
             return _i32([POS_UNDEFINED if x is None else int(x) for x in np.broadcast_to(np.asarray(a, object), (n,))])
-        s, e = arr(start), arr(end)
         r = None if ref_seq is None else _i32(np.broadcast_to(np.asarray(ref_seq), (n,)))
         c = None if client is None else _i32(np.broadcast_to(np.asarray(client), (n,)))
+        return n, d, arr(start), arr(end), r, c
+
+    def get_text_range(self, docs, start=None, end=None, ref_seq=None, client=None, placeholder: str = "") -> list[str]:
+        """mt_get_text_range: MergeTreeTextHelper.getText(ref_seq[i], client[i], placeholder,
+        start[i], end[i]) (MT/textSegment.ts:163-194) of each query, gathered on the device.
+        start / end: None (0 / the view's length) or a sequence whose elements may be None /
+        POS_UNDEFINED for undefined; a scalar is broadcast.  ref_seq None or < 0: the local view.
+        start > end gives what JS substring's swap gives (include/mtgpu.h).  Raw ABI: client is
+        the engine's per-document client index, and "*" is an ordinary one-unit placeholder."""
+        n, d, s, e, r, c = self._range_args(docs, start, end, ref_seq, client)
         ph = np.frombuffer(placeholder.encode("utf-16-le", "surrogatepass"), np.uint16)
         arena, off = ctypes.c_void_p(), ctypes.c_void_p()
-        ptr = lambda a: a.ctypes.data if a is not None and len(a) else None  # noqa: E731
-        self._check(self.fn["get_text_range"](self.h, n, ptr(d), ptr(s), ptr(e), ptr(r), ptr(c), ptr(ph), len(ph),
+        self._check(self.fn["get_text_range"](self.h, n, _ptr(d), _ptr(s), _ptr(e), _ptr(r), _ptr(c), _ptr(ph), len(ph),
                                               ctypes.byref(arena), ctypes.byref(off)), "mt_get_text_range")
         offs = np.ctypeslib.as_array(ctypes.cast(off, ctypes.POINTER(ctypes.c_uint64)), (n + 1,)).copy()
         raw = ctypes.string_at(arena, int(offs[-1]) * 2) if offs[-1] else b""
@@ -725,19 +736,9 @@ class Engine:
         start / end, ref_seq / client as get_text_range takes them; text False: no text is
         copied.  Returns a Walk: query i is walk[i] = (its WALK_REC_DTYPE records, their texts,
         their property maps).  Raw ABI: client is the engine's per-document client index."""
-        d = _u32(docs)
-        n = len(d)
-
-        def arr(a):
-            if a is None:
-                return None
-            return _i32([POS_UNDEFINED if x is None else int(x) for x in np.broadcast_to(np.asarray(a, object), (n,))])
-        s, e = arr(start), arr(end)
-        r = None if ref_seq is None else _i32(np.broadcast_to(np.asarray(ref_seq), (n,)))
-        c = None if client is None else _i32(np.broadcast_to(np.asarray(client), (n,)))
+        n, d, s, e, r, c = self._range_args(docs, start, end, ref_seq, client)
         recs, off, arena, maps = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-        ptr = lambda a: a.ctypes.data if a is not None and len(a) else None  # noqa: E731
-        self._check(self.fn["walk_segments"](self.h, n, ptr(d), ptr(s), ptr(e), ptr(r), ptr(c), MT_WALK_TEXT if text else 0,
+        self._check(self.fn["walk_segments"](self.h, n, _ptr(d), _ptr(s), _ptr(e), _ptr(r), _ptr(c), MT_WALK_TEXT if text else 0,
                                              ctypes.byref(recs), ctypes.byref(off), ctypes.byref(arena) if text else None,
                                              ctypes.byref(maps)), "mt_walk_segments")
         return Walk(self, n, recs, off, arena if text else None, maps)

@@ -150,6 +150,23 @@ def check_remote_view(factory):
     assert th.getText(0, 0, "_") == "_llo world"
     # everything seen at 4
     assert th.getText(4, a, "_") == "_llo world" and th.getText(4, b, "_", 1) == "llo world"
+    # A writes 70 one-unit rows (seq 1..70, msn 0: nothing merges) and a row of 65 units (seq 71); B
+    # removes the fourth row (seq 72).  A at 71 has not seen the remove, so its view holds 135 units
+    # and [68, 134) starts at the row of index 68: a unit of the scan holds 64 rows at the most, so
+    # the scan enters at a unit that is not the document's first and takes that unit's start from
+    # the row found there.  The range ends 64 units into the long row: 66 units, two rounds of 64.
+    long = "".join(chr(0x100 + k) for k in range(65))
+    g = ClientGroup(factory(1, **LIMITS))
+    c = g.new_client()
+    for k in range(70):
+        c.applyMsg(msg("A", k + 1, k, 0, ins(k, chr(0x41 + k % 26))))
+    c.applyMsg(msg("A", 71, 70, 0, ins(70, long)))
+    c.applyMsg(msg("B", 72, 71, 0, rem(3, 4)))
+    g.flush()
+    th, a = c.createTextHelper(), c.getShortClientId("A")
+    assert int(c.engine.pools([0])[0, 6]) == 2 and c.getLength() == 134 and len(th.getText(71, a, "")) == 135
+    assert th.getText(71, a, "", 68, 134) == "QR" + long[:64] and th.getText(71, a, "", 134, 68) == ""
+    assert c.getText(67, 133) == "QR" + long[:64]
 
 
 KNOWN = [check_plain_ranges, check_markers, check_swapped, check_surrogates_and_rounds, check_remote_view]

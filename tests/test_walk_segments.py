@@ -201,6 +201,27 @@ def check_remote_view(factory):
     recs, texts, _ = one(None, None, [1], [a])
     assert texts == ["llo"] and list(recs["pos"]) == [0] and list(recs["obs_pos"]) == [1] and list(recs["end"]) == [3]
     assert one([2], [1], [2], [b])[1] == [] and one([5], [4], [2], [b])[1] == ["llo"] and one([3], [3], [1], [a])[1] == []
+    # A writes 70 one-unit rows (seq 1..70, msn 0: nothing merges) and a row of 65 units (seq 71); B
+    # removes the fourth row (seq 72).  A at 71 has not seen the remove, so its view holds 135 units
+    # and [68, 134) starts at the row of index 68: a unit of the scan holds 64 rows at the most, so
+    # the scan enters at a unit that is not the document's first and takes that unit's start from
+    # the row found there.  The three visited rows' whole texts are 67 units: two rounds of 64.
+    long = "".join(chr(0x100 + k) for k in range(65))
+    g = ClientGroup(factory(1, **LIMITS))
+    c = g.new_client()
+    for k in range(70):
+        c.applyMsg(msg("A", k + 1, k, 0, ins(k, chr(0x41 + k % 26))))
+    c.applyMsg(msg("A", 71, 70, 0, ins(70, long)))
+    c.applyMsg(msg("B", 72, 71, 0, rem(3, 4)))
+    g.flush()
+    a = c.names.ids["A"]
+    assert int(c.engine.pools([0])[0, 6]) == 2 and c.getLength() == 134
+    recs, texts, _ = c.engine.walk_segments([0], [68], [134], [71], [a])[0]
+    assert texts == ["Q", "R", long] and list(recs["pos"]) == [68, 69, 70] and list(recs["len"]) == [1, 1, 65]
+    assert list(recs["start"]) == [0, -1, -2] and list(recs["end"]) == [66, 65, 64] and list(recs["text_off"]) == [0, 1, 2]
+    # the observer has seen the remove: its positions are one lower
+    assert list(recs["obs_pos"]) == [67, 68, 69] and list(recs["seq"]) == [69, 70, 71]
+    assert list(recs["removed_seq"]) == [POS_UNDEFINED] * 3 and len(c.engine.walk_segments([0], None, None, [71], [a])[0][0]) == 71
 
 
 KNOWN = [check_spec_cases, check_hand_derived, check_scan_shapes, check_remote_view]
