@@ -130,13 +130,21 @@ class PropTable:
         self._incr_keys: set[int] = set()      # keys some incr op names
         self._n_incr = 0                       # incr ops interned
         self._c = None
+        # Changes whenever what to_c() builds would: a new key, value or set, a key newly named by
+        # an incr op, or a deeper incr chain (_incr_table).  The hosts upload the table again when
+        # it differs from the version they uploaded, and only then.
+        self.version = 0
+
+    def _touch(self):
+        self._c = None
+        self.version += 1
 
     def key_id(self, k: str) -> int:
         i = self.key_ids.get(k)
         if i is None:
             i = self.key_ids[k] = len(self.keys)
             self.keys.append(k)
-            self._c = None
+            self._touch()
         return i
 
     def value_id(self, v: Any) -> int:
@@ -152,7 +160,7 @@ class PropTable:
             c = self._class_ids.setdefault(ck, len(self._class_ids))
             self.values_class.append(c)
             self.values_kind.append(value_kind(v))
-            self._c = None
+            self._touch()
         return i
 
     def intern(self, props: dict) -> int:
@@ -179,8 +187,13 @@ class PropTable:
                 code = self.value_id(mv) if below else self.value_id(r)
             fl = MT_OPF_COMBINE | (MT_OPF_INCR_STRMIN if str_min else 0)
             self._n_incr += 1
+            if self._n_incr <= INCR_CHAIN_MAX:      # the chains get one step deeper (_incr_table)
+                self._touch()
             for k in props.keys():
-                self._incr_keys.add(self.key_id(k))
+                ki = self.key_id(k)
+                if ki not in self._incr_keys:
+                    self._incr_keys.add(ki)
+                    self._touch()
         elif name == "consensus":           # {value: undefined, seq}; null.seq throws; seq -1 is set
             if not has_def:
                 code = MT_VAL_CFRESH
@@ -200,7 +213,7 @@ class PropTable:
         if i is None:
             i = self.set_ids[pairs] = len(self.sets)
             self.sets.append(pairs)
-            self._c = None
+            self._touch()
         return i
 
     def tile_match(self, labels) -> np.ndarray:

@@ -138,6 +138,7 @@ int MT_FN(checkpoint)(mt_ctx* c) {
         if (bytes) mtb_d2d(c, c->ck[k], mt_pool_get(c->S, MT_POOLS[k]), bytes);
     }
     c->ck_layout = c->layout_h; c->ck_tot = c->tot; c->ck_dead = c->dead;
+    c->ck_doc_keys = c->doc_keys; c->ck_doc_wide = c->doc_wide; c->ck_props_wide = c->props_wide;
     c->ck_valid = true;
     return MT_OK;
 }
@@ -158,6 +159,31 @@ int MT_FN(restore)(mt_ctx* c) {
         rc = mt_rederive(c);
     }
     c->tot = c->ck_tot; c->dead = c->ck_dead;
+    // The maps are the checkpoint's again, so the keys counted for them count again: a document
+    // wide then is wide now, whatever mt_docs_open cleared since.  If the table first passed
+    // MT_WAVE keys after the checkpoint, nobody counted the checkpoint's keys (as in mt_set_props).
+    // The marks only ever err towards wide: what was counted since the checkpoint stays counted
+    // (the resident batch, counted once at its upload, may be replayed onto the restored maps), so
+    // each document gets the union of the two counts.
+    if (c->props_wide) {
+        if (c->doc_wide.size() < c->S.maxDocs) { c->doc_wide.resize(c->S.maxDocs, 0); c->doc_keys.resize(c->S.maxDocs); }
+        if (c->ck_props_wide && c->ck_doc_wide.size() == c->doc_wide.size()) {
+            for (size_t d = 0; d < c->doc_wide.size(); d++) {
+                if (c->doc_wide[d]) continue;
+                std::vector<uint16_t>& ks = c->doc_keys[d];
+                const std::vector<uint16_t>& ck = c->ck_doc_keys[d];
+                if (!ck.empty()) {
+                    std::vector<uint16_t> u(ks.size() + ck.size());
+                    u.resize((size_t)(std::set_union(ks.begin(), ks.end(), ck.begin(), ck.end(), u.begin()) - u.begin()));
+                    ks.swap(u);
+                }
+                if (c->ck_doc_wide[d] || ks.size() > MT_WAVE) { c->doc_wide[d] = 1; std::vector<uint16_t>().swap(ks); }
+            }
+        } else {
+            std::fill(c->doc_wide.begin(), c->doc_wide.end(), (uint8_t)1);
+            for (auto& k : c->doc_keys) std::vector<uint16_t>().swap(k);
+        }
+    }
     return rc;
 }
 int MT_FN(pool_bytes)(mt_ctx* c, uint64_t* bytes) {
@@ -491,8 +517,15 @@ static bool mt_scan_wide(mt_ctx* c, size_t n_runs, DocOf doc, Op0 op0, Op1 op1, 
 }
 }
 // Device-built batches (the generators, the exchange: ops never seen on the host): wide when the
-// property sets together could make a document wide.
-static bool mt_dev_wide(const mt_ctx* c) { return c->props_wide; }
+// property sets together could make a document wide.  Nobody counts the keys such a batch names,
+// so its documents are wide from then on (sticky, as mt_note_set's): a later host batch for one of
+// them replays in the FULL kernels too, some of them without need.
+static bool mt_dev_wide(mt_ctx* c, uint32_t n_runs, const uint32_t* doc_ids) {
+    if (!c->props_wide) return false;
+    if (c->doc_wide.size() < c->S.maxDocs) { c->doc_wide.resize(c->S.maxDocs, 0); c->doc_keys.resize(c->S.maxDocs); }
+    for (uint32_t r = 0; r < n_runs; r++) { c->doc_wide[doc_ids[r]] = 1; std::vector<uint16_t>().swap(c->doc_keys[doc_ids[r]]); }
+    return true;
+}
 // Such a batch's arrays (b_doc, b_off, b_rec, b_pay; per-run payload bases in b_pbase): generated
 // and exchanged streams hold no relative positions, and no register ops either.
 static MtOps mt_dev_ops(mt_ctx* c, uint32_t n_runs, uint64_t payload_units, bool pay_base) {
@@ -530,12 +563,13 @@ static MtOps mt_staged_ops(uint8_t* d, const MtStageLayout& y, size_t R, size_t 
 // mt_generate_docs launches with them clear).  keep_gen: a host upload leaves gen.enabled (and
 // gen_docs) as they are, as it always did, so mt_generated_to_resident still answers for the
 // last generated stream; a device-built batch disarms the generator.
-static void mt_install_batch(mt_ctx* c, MtOps o, const uint32_t* run_off, bool reg, bool wide, bool keep_gen) {
+static void mt_install_batch(mt_ctx* c, MtOps o, const uint32_t* run_off, const uint32_t* run_docs, bool reg, bool wide, bool keep_gen) {
     o.drec = nullptr; o.dcount = nullptr; o.dcap = 0; o.dtext = nullptr; o.dtcap = 0;
     o.resume = nullptr; o.start = nullptr; o.grow_pch = 0;
     c->ops = o;
     c->n_runs = o.n_runs;
     c->run_off.assign(run_off, run_off + o.n_runs + 1); c->batch_gen++;
+    c->run_docs.assign(run_docs, run_docs + o.n_runs); c->batch_dev = !keep_gen; c->batch_replays = 0;
     c->batch_reg = reg; c->batch_wide = wide;
     if (!keep_gen) c->gen.enabled = 0;
 }
@@ -543,7 +577,7 @@ static void mt_install_batch(mt_ctx* c, MtOps o, const uint32_t* run_off, bool r
 // (mtb_ensure): no batch is resident (mt_replay_resident: MT_E_INVALID), and none generated.
 static int mt_drop_batch(mt_ctx* c, int rc) {
     c->ops = MtOps{};
-    c->n_runs = 0; c->run_off.clear(); c->batch_gen++;
+    c->n_runs = 0; c->run_off.clear(); c->run_docs.clear(); c->batch_dev = false; c->batch_replays = 0; c->batch_gen++;
     c->batch_reg = c->batch_wide = false;
     c->gen.enabled = 0; c->gen_docs = 0;
     return rc;
@@ -601,7 +635,7 @@ static int mt_upload_ops(mt_ctx* c, const mt_op_batch* B) {
     mtb_stage_send(c, c->b_batch.p, y.total);
     const bool wide = mt_scan_wide(c, R, [&](size_t r) { return B->doc_ids[r]; }, [&](size_t r) { return B->op_offsets[r]; },
                                    [&](size_t r) { return B->op_offsets[r + 1]; }, [&](size_t i) { return B->prop_id[i]; });
-    mt_install_batch(c, mt_staged_ops((uint8_t*)c->b_batch.p, y, R, PU, NR), B->op_offsets, reg, wide, true);
+    mt_install_batch(c, mt_staged_ops((uint8_t*)c->b_batch.p, y, R, PU, NR), B->op_offsets, B->doc_ids, reg, wide, true);
     return MT_OK;
 }
 
@@ -707,7 +741,7 @@ static int mt_upload_parts(mt_ctx* c, uint32_t P, const mt_op_batch* parts, cons
     mtb_stage_send(c, c->b_batch.p, y.total);
     const bool wide = mt_scan_wide(c, R, [&](size_t r) { return docs[r]; }, [&](size_t r) { return (size_t)runOff[r]; },
                                    [&](size_t r) { return (size_t)runOff[r + 1]; }, [&](size_t i) { return (int)rec[i].prop_id; });
-    mt_install_batch(c, mt_staged_ops((uint8_t*)c->b_batch.p, y, R, PU, NR), runOff.data(), reg, wide, true);
+    mt_install_batch(c, mt_staged_ops((uint8_t*)c->b_batch.p, y, R, PU, NR), runOff.data(), docs, reg, wide, true);
     return MT_OK;
 }
 int MT_FN(upload_batch_parts)(mt_ctx* c, uint32_t n_parts, const mt_op_batch* parts, const int32_t* const* prop_map,
@@ -843,6 +877,17 @@ int MT_FN(replay_resident)(mt_ctx* c) {
     if (rc) return rc;
     MtGen g{}; g.enabled = 0;
     c->delta_valid = false;
+    // While the table is wide, the marks must hold for what this replay builds.  A device-built
+    // batch was never counted, and a host batch was counted once, at its upload: replayed again
+    // (after mt_docs_open cleared the marks, or onto maps an mt_restore brought back) its count
+    // stands for nothing, so its documents end wide (sticky).  And a batch uploaded before a
+    // document of it was marked (mt_set_props turning the table wide, a restore) is wide now.
+    if (c->props_wide && c->run_docs.size() == c->n_runs) {
+        if (c->batch_dev || c->batch_replays) c->batch_wide = mt_dev_wide(c, c->n_runs, c->run_docs.data()) || c->batch_wide;
+        for (uint32_t r = 0; r < c->n_runs && !c->batch_wide; r++)
+            c->batch_wide = c->run_docs[r] < c->doc_wide.size() && c->doc_wide[c->run_docs[r]];
+    }
+    c->batch_replays++;
     if (c->delta_cap || c->autogrow) return mt_replay_capture(c, g);
     c->ops.drec = nullptr; c->ops.dcount = nullptr; c->ops.dcap = 0; c->ops.dtext = nullptr; c->ops.dtcap = 0;
     c->ops.resume = nullptr; c->ops.start = nullptr; c->ops.grow_pch = 0;
@@ -1831,11 +1876,12 @@ int MT_FN(generate_docs)(mt_ctx* c, const mt_gen_params* P, const uint32_t* ops_
     mtb_h2d(c, c->b_off.p, off.data(), 4ull * (P->n_docs + 1));
     mtb_h2d(c, c->b_gencl.p, cl.data(), 4ull * P->n_docs);
     c->gen_off.assign(off.begin(), off.end());
-    mt_install_batch(c, mt_dev_ops(c, P->n_docs, PU, false), off.data(), false, mt_dev_wide(c), false);   // (armed below)
+    mt_install_batch(c, mt_dev_ops(c, P->n_docs, PU, false), off.data(), docs.data(), false, c->props_wide, false);   // (armed below)
     if (!P->continue_docs) {
         rc = MT_FN(docs_open)(c, 0, P->n_docs);
         if (rc) return rc;
     }
+    mt_dev_wide(c, P->n_docs, docs.data());             // after mt_docs_open, which clears the marks
     MtGen g{};
     g.seed = P->seed; g.ops = P->ops_per_doc; g.clients = P->clients; g.lag_max = P->lag_max;
     g.pct_insert = P->pct_insert; g.pct_remove = P->pct_remove; g.ins_len_max = P->ins_len_max;
@@ -1896,7 +1942,7 @@ int MT_FN(upload_batch_dev)(mt_ctx* c, uint32_t n_runs, const uint32_t* doc_ids,
     mtb_h2d(c, c->b_off.p, op_offsets, 4ull * (n_runs + 1));
     if (N) mtb_d2d(c, c->b_rec.p, rec, sizeof(MtOpRec) * N);
     if (payload_units) mtb_d2d(c, c->b_pay.p, payload, 2 * payload_units);
-    mt_install_batch(c, mt_dev_ops(c, n_runs, payload_units, false), op_offsets, false, mt_dev_wide(c), false);
+    mt_install_batch(c, mt_dev_ops(c, n_runs, payload_units, false), op_offsets, doc_ids, false, mt_dev_wide(c, n_runs, doc_ids), false);
     return mtb_sync(c);
 }
 // Document exchange rows (mt_shard.h): the sender packs generated runs at their plan
@@ -1944,7 +1990,7 @@ int MT_FN(upload_rows_dev)(mt_ctx* c, uint32_t n_runs, const uint32_t* doc_ids, 
         for (uint32_t r = 0; r < n_runs; r++) pbase[r] = (unsigned long long)op_offsets[r] * L;
         if (n_runs) mtb_h2d(c, c->b_pbase.p, pbase.data(), 8ull * n_runs);
     }
-    mt_install_batch(c, mt_dev_ops(c, n_runs, N * L, true), op_offsets, false, mt_dev_wide(c), false);
+    mt_install_batch(c, mt_dev_ops(c, n_runs, N * L, true), op_offsets, doc_ids, false, mt_dev_wide(c, n_runs, doc_ids), false);
     if (n_runs && (rc = mtb_launch_rows(c, false, 0, n_runs, (uint32_t)L, nullptr, (uint64_t*)rows_dev,
                                         (uint64_t*)c->b_tmp1.p))) return rc;
     if ((rc = mtb_sync(c))) return rc;

@@ -62,6 +62,9 @@ struct mt_ctx {
     uint32_t n_runs = 0;
     std::vector<uint32_t> run_off;     // host copy of the resident batch's op offsets (n_runs + 1)
     uint64_t batch_gen = 0;            // bumped whenever a batch becomes resident
+    std::vector<uint32_t> run_docs;    // host copy of the resident batch's document ids (n_runs)
+    bool batch_dev = false;            // the resident batch was built on the device: the host never saw its ops
+    uint32_t batch_replays = 0;        // mt_replay_resident calls on the resident batch so far
     // What follows feeds the replay plan (mt_plan.h mt_plan_replay), which alone decides the
     // launches of a batch; the streams and events are the HIP backend's lanes for them.
     // Size classes (mt_set_size_class): runs of at least big_min_ops op records replay in the
@@ -105,6 +108,9 @@ struct mt_ctx {
     bool props_wide = false;           // the property sets name more than MT_WAVE distinct keys
     std::vector<uint32_t> h_set_off; std::vector<uint16_t> h_set_key;
     std::vector<std::vector<uint16_t>> doc_keys; std::vector<uint8_t> doc_wide;
+    // mt_checkpoint's copies: mt_restore brings the device maps back, and with them what the
+    // host knew of their keys (whatever mt_docs_open cleared since)
+    std::vector<std::vector<uint16_t>> ck_doc_keys; std::vector<uint8_t> ck_doc_wide; bool ck_props_wide = false;
     int use_lds = 2, lds_rows = MT_L_ROWS, lds_blks = MT_B_BLKS, lds_heap = MT_B_HEAP;
     void* stream = nullptr;
     void* ev0 = nullptr;

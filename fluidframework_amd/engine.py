@@ -268,7 +268,7 @@ class Engine:
             self.props = props
         self._props_c = self.props.to_c()
         self._check(self.fn["set_props"](self.h, ctypes.byref(self._props_c)), "mt_set_props")
-        self._props_uploaded = len(self.props.sets)
+        self._props_uploaded = self.props.version       # after to_c(), which may intern incr strings
 
     def upload_names(self, literals: list[str] | None = None):
         lits = literals if literals is not None else self.names.json_literals()
@@ -285,13 +285,13 @@ class Engine:
 
     # ---- replay ----
     def apply(self, batch: OpBatch):
-        if self._props_uploaded != len(self.props.sets):
+        if self._props_uploaded != self.props.version:
             self.upload_props()
         self._batch = batch  # keep host arrays alive until sync
         self._check(self.fn["apply_batch"](self.h, ctypes.byref(batch.to_c())), "mt_apply_batch")
 
     def upload(self, batch: OpBatch):
-        if self._props_uploaded != len(self.props.sets):
+        if self._props_uploaded != self.props.version:
             self.upload_props()
         self._batch = batch
         self._check(self.fn["upload_batch"](self.h, ctypes.byref(batch.to_c())), "mt_upload_batch")
@@ -604,9 +604,10 @@ class Engine:
     # ---- tile search (include/mtgpu.h mt_find_tile / mt_tile_index) ----
     def _tile_labels(self, label: str) -> MtTileLabels:
         """mt_tile_labels of one label, built once and kept until the prop table grows."""
-        if self._props_uploaded != len(self.props.sets) or getattr(self, "_tile_nvalues", -1) != len(self.props.values_json):
-            self.upload_props()
-            self._tile_cache, self._tile_nvalues = {}, len(self.props.values_json)
+        if self._props_uploaded != self.props.version or getattr(self, "_tile_version", -1) != self.props.version:
+            if self._props_uploaded != self.props.version:
+                self.upload_props()
+            self._tile_cache, self._tile_version = {}, self.props.version
         t = self._tile_cache.get(label)
         if t is None:
             from .batch import TILE_LABELS_KEY

@@ -46,10 +46,20 @@ class PropTable {
         this.classIds = new Map();
         this.setIds = new Map(); this.sets = [];
         this.incrKeys = new Set(); this.nIncr = 0;
+        // Changes whenever what toNative() builds would: a new key, value or set, a key newly named
+        // by an incr op, or a deeper incr chain (incrTable).  Engine uploads the table again when
+        // it differs from the version it uploaded, and only then.
+        this.version = 0;
+    }
+    /** `n` more incr ops naming the keys `keyIds` (incrTable's inputs). */
+    addIncr(n, keyIds) {
+        if (n > 0 && this.nIncr < INCR_CHAIN_MAX) this.version++;      // the chains get deeper
+        this.nIncr += n;
+        for (const k of keyIds) if (!this.incrKeys.has(k)) { this.incrKeys.add(k); this.version++; }
     }
     keyId(k) {
         let i = this.keyIds.get(k);
-        if (i === undefined) { i = this.keys.length; this.keyIds.set(k, i); this.keys.push(k); }
+        if (i === undefined) { i = this.keys.length; this.keyIds.set(k, i); this.keys.push(k); this.version++; }
         return i;
     }
     valueId(v) {
@@ -66,6 +76,7 @@ class PropTable {
             if (c === undefined) { c = this.classIds.size; this.classIds.set(ck, c); }
             this.valueClass.push(c);
             this.valueKind.push((isNumberLike(v) ? VK_NUM : 0) | (seqMinus1(v) ? VK_SEQM1 : 0));
+            this.version++;
         }
         return i;
     }
@@ -110,8 +121,7 @@ class PropTable {
                 code = this.valueId(r);
             }
             fl = F_COMBINE | (strMin ? F_INCR_STRMIN : 0);
-            this.nIncr++;
-            for (const k of Object.keys(props)) this.incrKeys.add(this.keyId(k));
+            this.addIncr(1, Object.keys(props).map((k) => this.keyId(k)));
         } else if (cop.name === "consensus") {              // {value: undefined, seq}; null.seq throws
             code = d === undefined ? VAL_CFRESH : (d === null ? VAL_THROW : this.valueId(seqMinus1(d) ? { ...d, seq } : d));
             fl = F_COMBINE | F_REWRITE | F_CONSENSUS;
@@ -124,7 +134,7 @@ class PropTable {
     internPairs(pairs) {
         const sig = pairs.map((p) => p.join(":")).join(",");
         let i = this.setIds.get(sig);
-        if (i === undefined) { i = this.sets.length; this.setIds.set(sig, i); this.sets.push(pairs); }
+        if (i === undefined) { i = this.sets.length; this.setIds.set(sig, i); this.sets.push(pairs); this.version++; }
         return i;
     }
     /**

@@ -201,16 +201,13 @@ class Engine {
         this.maxDocs = maxDocs;
         this.h = addon.create(device, { ...DEFAULT_LIMITS, ...limits, maxDocs });
         this.props = new PropTable();
-        this.uploadedSets = -1;
+        this.uploadedVersion = -1;       // PropTable.version of the table the device holds
     }
     close() { if (this.h) { addon.destroy(this.h); this.h = null; } }
     openDocs(first, n) { addon.docsOpen(this.h, first, n); }
     setClientNames(jsonLiterals) { addon.setClientNames(this.h, jsonLiterals); }
     apply(batch) {
-        if (this.uploadedSets !== this.props.sets.length) {
-            addon.setProps(this.h, this.props.toNative());
-            this.uploadedSets = this.props.sets.length;
-        }
+        this.uploadProps();
         addon.applyBatch(this.h, batch);
     }
     /** Several packed parts applied as one batch (mt_apply_batch_parts; ParallelPacker.packHeldParts). */
@@ -219,9 +216,9 @@ class Engine {
         addon.applyBatchParts(this.h, parts, propMaps);
     }
     uploadProps() {
-        if (this.uploadedSets !== this.props.sets.length) {
+        if (this.uploadedVersion !== this.props.version) {
             addon.setProps(this.h, this.props.toNative());
-            this.uploadedSets = this.props.sets.length;
+            this.uploadedVersion = this.props.version;      // after toNative(), which may intern incr strings
         }
     }
     loadSnapshot(batch) { this.uploadProps(); addon.loadSnapshot(this.h, batch); }

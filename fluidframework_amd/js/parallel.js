@@ -124,8 +124,7 @@ class ParallelPacker {
 // the non-value codes of combine sets (MT_VAL_*, negative) kept as they are.
 function absorb(wp, props) {
     // the keys incr ops name, and their count (PropTable.incrTable's inputs)
-    for (const k of wp.incrKeys || []) props.incrKeys.add(props.keyId(wp.keys[k]));
-    props.nIncr += wp.nIncr || 0;
+    props.addIncr(wp.nIncr || 0, [...(wp.incrKeys || [])].map((k) => props.keyId(wp.keys[k])));
     return Int32Array.from(wp.sets.map((pairs) => props.internPairs(pairs.map(([k, v]) =>
         [props.keyId(wp.keys[k]), v < 0 ? v : props.valueId(JSON.parse(wp.valueJson[v]))]))));
 }

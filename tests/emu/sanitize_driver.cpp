@@ -178,6 +178,105 @@ static void run(const Scenario& sc, Props& P) {
     fprintf(stderr, "%-28s %u docs x %u msgs: %s\n", sc.name, n, k, fails ? "FAILED" : "ok");
 }
 
+// Wide-key tracking across lifecycle calls (mt_ctx::doc_wide and its checkpoint copies): 24
+// annotates of 4 keys of their own make one segment's map 96 keys wide; checkpoint, reopen,
+// restore, then a narrow annotate in a batch of its own, which must replay in the kernels that
+// build wide maps (status 0, the oracle's digest for both batches in one).  `again` repeats the
+// restore after two more batches, with the checkpoint's vectors copied a second time.
+static void run_wide_lifecycle() {
+    const Scenario sc{"wide maps: checkpoint, reopen, restore", 2, 26, 1, 0, 0, 0, 8, 8, 0, 2, 0, false};
+    const int NS = 24, NK = 4 * NS;
+    std::vector<std::string> ks; std::vector<const char*> kj; std::vector<uint32_t> kidx(NK, 0xFFFFFFFFu), off{0};
+    std::vector<uint16_t> key; std::vector<int32_t> val;
+    for (int i = 0; i < NK; i++) ks.push_back("\"w" + std::to_string(i) + "\"");
+    for (auto& s : ks) kj.push_back(s.c_str());
+    for (int s = 0; s < NS; s++) { for (int i = 0; i < 4; i++) { key.push_back((uint16_t)(4 * s + i)); val.push_back(s % 2); } off.push_back((uint32_t)key.size()); }
+    const char* vj[2] = {"\"a\"", "\"b\""};
+    const uint8_t falsy[2] = {0, 0}, kind[2] = {0, 0};
+    const uint32_t cls[2] = {0, 1};
+    const int32_t incr[2] = {MT_VAL_UNSUP, MT_VAL_UNSUP};
+    mt_prop_table t{};
+    t.n_sets = NS; t.set_off = off.data(); t.key = key.data(); t.value = val.data(); t.n_keys = NK; t.key_json = kj.data();
+    t.key_index = kidx.data(); t.n_values = 2; t.value_json = vj; t.value_falsy = falsy; t.value_class = cls; t.value_kind = kind;
+    t.value_incr = incr; t.incr_object = MT_VAL_UNSUP;
+    // document 0: an insert, 24 annotates of the whole text, then the narrow annotate [2, 5) of set 1;
+    // document 1 rides along narrow (one insert, one annotate)
+    const uint32_t N0 = 1 + NS + 1, N = N0 + 2;
+    std::vector<uint8_t> type(N, MT_OP_ANNOTATE), flags(N, MT_OPF_END_OF_MSG); std::vector<uint16_t> client(N, 0);
+    std::vector<int32_t> seq(N), ref(N), msn(N, 0), p1(N, 0), p2(N, 8), pid(N, -1);
+    std::vector<uint32_t> poff(N, 0), plen(N, 0);
+    const uint16_t payload[8] = {'a', 'b', 'c', 'd', 'e', 'f', 'g', 'h'};
+    for (uint32_t i = 0; i < N0; i++) { seq[i] = (int)i + 1; ref[i] = (int)i; if (i) pid[i] = (int)(i - 1) % NS; }
+    type[0] = MT_OP_INSERT; p2[0] = 0; plen[0] = 8;
+    p1[N0 - 1] = 2; p2[N0 - 1] = 5; pid[N0 - 1] = 1;
+    type[N0] = MT_OP_INSERT; p2[N0] = 0; plen[N0] = 8; seq[N0] = 1; ref[N0] = 0;
+    seq[N0 + 1] = 2; ref[N0 + 1] = 1; pid[N0 + 1] = 3;
+    auto view = [&](uint32_t lo, uint32_t hi, const uint32_t* ids, const uint32_t* ro, uint32_t runs) {
+        mt_op_batch b{};
+        b.n_runs = runs; b.doc_ids = ids; b.op_offsets = ro; b.n_ops = hi - lo; b.type = &type[lo]; b.flags = &flags[lo];
+        b.client = &client[lo]; b.seq = &seq[lo]; b.ref_seq = &ref[lo]; b.msn = &msn[lo]; b.pos1 = &p1[lo]; b.pos2 = &p2[lo];
+        b.payload_off = &poff[lo]; b.payload_len = &plen[lo]; b.prop_id = &pid[lo]; b.payload = payload; b.payload_units = 8;
+        return b;
+    };
+    const uint32_t id0[1] = {0}, id1[1] = {1}, both[2] = {0, 1};
+    const uint32_t roWide[2] = {0, N0 - 1}, roNarrow[2] = {0, 1}, roDoc1[2] = {0, 2}, roAll[3] = {0, N0, N};
+    mt_limits L{}; L.max_docs = 2; L.rows_per_doc = 256; L.blocks_per_doc = 64; L.heap_per_doc = 128; L.window_per_doc = 256;
+    L.text_per_doc = 1024; L.propsets_per_doc = 2048;
+    mt_ctx* c = nullptr;
+    CHECK(emu_create(0, &L, &c) == MT_OK, "create");
+    CHECK(emu_set_props(c, &t) == MT_OK, "set_props");
+    const char* names[1] = {"\"c0\""};
+    emu_set_client_names(c, 1, names);
+    CHECK(emu_docs_open(c, 0, 2) == MT_OK, "open");
+    mt_op_batch wide = view(0, N0 - 1, id0, roWide, 1), narrow = view(N0 - 1, N0, id0, roNarrow, 1), doc1 = view(N0, N, id1, roDoc1, 1);
+    CHECK(emu_apply_batch(c, &wide) == MT_OK, "wide batch");
+    for (int again = 0; again < 2; again++) {
+        CHECK(emu_checkpoint(c) == MT_OK, "checkpoint");
+        if (again) {                                  // batches after the checkpoint, undone by the restore
+            CHECK(emu_apply_batch(c, &narrow) == MT_OK, "narrow batch before the restore");
+            CHECK(emu_apply_batch(c, &doc1) == MT_OK, "document 1 before the restore");
+        }
+        CHECK(emu_docs_open(c, 0, 1) == MT_OK, "reopen");
+        CHECK(emu_restore(c) == MT_OK, "restore");
+    }
+    CHECK(emu_apply_batch(c, &narrow) == MT_OK, "narrow batch");
+    CHECK(emu_apply_batch(c, &doc1) == MT_OK, "document 1");
+    emu_sync(c);
+    uint32_t st[2] = {~0u, ~0u};
+    emu_doc_status(c, 2, both, st);
+    int32_t neg[2] = {-1, -1};
+    uint64_t dig[2] = {0, 0}, odg[2] = {0, 0}; uint32_t ost[2] = {~0u, ~0u};
+    const char* arena; const uint64_t* boff; const uint32_t* bfirst;
+    mt_op_batch all = view(0, N, both, roAll, 2);
+    ora_replay_batch(&all, &t, 1, odg, ost, nullptr);
+    CHECK(st[0] == 0 && st[1] == 0 && ost[0] == 0 && ost[1] == 0, "status %#x %#x, oracle %#x %#x", st[0], st[1], ost[0], ost[1]);
+    CHECK(emu_snapshot_v1(c, 2, both, neg, neg, dig, &arena, &boff, &bfirst) == MT_OK, "snapshot");
+    CHECK(dig[0] == odg[0] && dig[1] == odg[1], "SnapshotV1 digests vs oracle");
+    CHECK(memmem(arena, boff[bfirst[2]], "\"w95\"", 5) != nullptr, "the snapshot holds no 96-key map");
+    emu_destroy(c);
+    // The same stream with the checkpoint before the wide batch, which is uploaded once and
+    // replayed on both sides of the restore (mt_upload_batch + mt_replay_resident): the count
+    // made at the upload must outlive the restore.
+    const uint32_t roIns[2] = {0, 1}, roAnn[2] = {0, N0 - 2};
+    mt_op_batch first = view(0, 1, id0, roIns, 1), anns = view(1, N0 - 1, id0, roAnn, 1);
+    CHECK(emu_create(0, &L, &c) == MT_OK, "create");
+    CHECK(emu_set_props(c, &t) == MT_OK, "set_props");
+    emu_set_client_names(c, 1, names);
+    CHECK(emu_docs_open(c, 0, 2) == MT_OK, "open");
+    CHECK(emu_apply_batch(c, &first) == MT_OK, "insert");
+    CHECK(emu_checkpoint(c) == MT_OK, "checkpoint before the wide batch");
+    CHECK(emu_upload_batch(c, &anns) == MT_OK && emu_replay_resident(c) == MT_OK, "upload and replay");
+    CHECK(emu_restore(c) == MT_OK && emu_replay_resident(c) == MT_OK, "restore and replay again");
+    CHECK(emu_apply_batch(c, &narrow) == MT_OK, "narrow batch after the second replay");
+    emu_sync(c);
+    emu_doc_status(c, 1, id0, st);
+    CHECK(st[0] == 0, "status %#x after restore and replay_resident", st[0]);
+    CHECK(emu_snapshot_v1(c, 1, id0, neg, neg, dig, &arena, &boff, &bfirst) == MT_OK, "snapshot");
+    CHECK(dig[0] == odg[0], "SnapshotV1 digest vs oracle after restore and replay_resident");
+    emu_destroy(c);
+    fprintf(stderr, "%-28s %s\n", sc.name, fails ? "FAILED" : "ok");
+}
+
 int main() {
     Props P;
     const Scenario S[] = {
@@ -193,6 +292,7 @@ int main() {
         {"combining annotates, wide blk", 4, 3000, 8, 8, 30, 30, 8, 16, 5, 2, 0, false, 1000, true},
     };
     for (const auto& s : S) run(s, P);
+    run_wide_lifecycle();
     if (fails) { fprintf(stderr, "%d checks failed\n", fails); return 1; }
     fprintf(stderr, "sanitize_driver: every scenario equal to the oracle, no sanitizer report\n");
     return 0;

@@ -9,6 +9,11 @@ const fs = require("fs");
 const path = require("path");
 const mt = require(path.join(__dirname, "..", "..", "fluidframework_amd", "js"));
 
+// mt_set_props calls, counted on this side (Engine.uploadProps goes through the addon object)
+let propUploads = 0;
+const setProps = mt.addon.setProps;
+mt.addon.setProps = (...a) => { propUploads++; return setProps(...a); };
+
 const [inPath, outPath] = process.argv.slice(2);
 const spec = JSON.parse(fs.readFileSync(inPath, "utf8"));
 const eng = new mt.Engine(spec.docs.length, spec.limits || {});
@@ -20,7 +25,15 @@ const clients = spec.docs.map(() => {
 });
 // optional: load a snapshot into each document first (Client.load / SnapshotLoader)
 if (spec.loads) spec.loads.forEach((blobs, d) => { if (blobs) clients[d].loadBlobs(blobs); });
-spec.docs.forEach((msgs, d) => { for (const m of msgs) clients[d].applyMsg(m); });
+// optional: spec.schedule[f][d] messages of document d before flush f (a stream cut into
+// batches: documents receive different numbers of messages per flush, some none); what the
+// schedule leaves over follows in one last flush, as does everything without a schedule
+const at = spec.docs.map(() => 0);
+for (const counts of spec.schedule || []) {
+    counts.forEach((n, d) => { for (; n > 0 && at[d] < spec.docs[d].length; n--) clients[d].applyMsg(spec.docs[d][at[d]++]); });
+    group.flush();
+}
+spec.docs.forEach((msgs, d) => { for (; at[d] < msgs.length; at[d]++) clients[d].applyMsg(msgs[at[d]]); });
 const out = { texts: [], lengths: [], blobs: [], digests: [], legacy: [] };
 clients.forEach((c, d) => {
     out.texts.push(c.getText());
@@ -60,5 +73,7 @@ const legacyFormat = (spec.options || { newMergeTreeSnapshotFormat: true }).newM
 const snaps = eng.snapshot(clients.map((c) => c.docId), clients.map((c) => c.minSeq), clients.map((c) => c.getCurrentSeq()),
     legacyFormat);
 out.digests = snaps.map((s) => s.digest.toString(16));
+out.propUploads = propUploads;
+out.propVersion = eng.props.version;
 fs.writeFileSync(outPath, JSON.stringify(out));
 eng.close();

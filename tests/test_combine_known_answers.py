@@ -153,11 +153,15 @@ CASES = [
 ]
 
 
-def run_engine(factory, msgs, options=None):
+def run_engine(factory, msgs, options=None, flush_each=False):
+    """flush_each: every message is its own batch (a live client's flush per message), so what
+    the host interns for one message reaches the device before the next."""
     g = ClientGroup(factory(1, **LIMITS))
     c = g.new_client(options or {"newMergeTreeSnapshotFormat": True})
     for m in msgs:
         c.applyMsg(m)
+        if flush_each:
+            g.flush()
     g.flush()
     return g, c
 
@@ -178,9 +182,9 @@ def test_combine_known_answers_oracle(name, ops, want):
     assert props_texts(blobs) == want
 
 
-def check_engine_case(factory, ops, want):
+def check_engine_case(factory, ops, want, flush_each=False):
     msgs = stream_of(ops, msn_lag=0)
-    g, _ = run_engine(factory, msgs)
+    g, _ = run_engine(factory, msgs, flush_each=flush_each)
     st = int(g.engine.status([0])[0])
     if isinstance(want, int):
         assert st & want, st
@@ -208,6 +212,19 @@ def test_combine_known_answers_on_emulation(name, ops, want):
 @pytest.mark.parametrize("name,ops,want", CASES, ids=[c[0] for c in CASES])
 def test_combine_known_answers_on_gpu(name, ops, want):
     check_engine_case(lambda n, **kw: Engine(n, device=0, **kw), ops, want)
+
+
+# The same answers with a flush after every message: the property table grows between launches
+# (sets, values, and the incr chains of PropTable._incr_table, which no new set announces).
+@pytest.mark.parametrize("name,ops,want", CASES, ids=[c[0] for c in CASES])
+def test_combine_known_answers_per_message_on_emulation(name, ops, want):
+    check_engine_case(emu_engine, ops, want, flush_each=True)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,ops,want", CASES, ids=[c[0] for c in CASES])
+def test_combine_known_answers_per_message_on_gpu(name, ops, want):
+    check_engine_case(lambda n, **kw: Engine(n, device=0, **kw), ops, want, flush_each=True)
 
 
 def test_zamboni_keeps_nan_segments_apart_on_emulation():
