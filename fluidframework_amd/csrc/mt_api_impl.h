@@ -14,9 +14,10 @@
 //   mt_plan.h, included after the above; mtb_launch_replay(c, gen, n_runs): the generator, or its plan
 //   mtb_launch_open(c, first, n), mtb_launch_load(c, load, n)
 //   mtb_launch_update_seq(c, docs, msn, seq, n), mtb_launch_get_length(c, docs, ref, cli, out, n)
-//   mtb_launch_query(c, q, groups, out, n_groups), mtb_launch_gather_text(c, at, len, off, dst, n)
+//   mtb_launch_gather_text(c, at, len, off, dst, n)
 //   mtb_launch_pack_size(c, docs, out, n, epoch), mtb_launch_pack(c, docs, off, stage, n, epoch)
 //   mtb_launch_rows(c, pack, first, n, L, dst, rows, checksums)
+//   with MTB_HAVE_QUERY: mtb_launch_query(c, call, q, groups, out, n_groups), the call's record by value
 //   with MTB_HAVE_RELOCATE: mtb_launch_occupancy(c, docs, out, n, epoch), mtb_launch_relocate(c, docs, ny, n, epoch, compact)
 #pragma once
 #include <algorithm>
@@ -1206,6 +1207,8 @@ int MT_FN(get_length)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t
 // written here from the text and the property-map chunks the kernel copied.
 // kind: MT_QK_LOCAL for position queries (a caller's ref_seq < 0 is the local view whatever its
 // value), else the tile-search kind every query of the call carries in `ref` (mt_query.h).
+// A call's arguments beyond the pools travel in an MtQueryCall that the entry point builds on its
+// stack and every launch takes by value: nothing here writes c->S.
 // The staging both query paths share: the queries sorted by document into q (ord[k]: the caller's
 // index of sorted query k), their groups uploaded with them.  ng: the groups.
 static int mt_stage_queries(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t* pos, const int32_t* ref,
@@ -1232,8 +1235,19 @@ static int mt_stage_queries(mt_ctx* c, uint32_t n, const uint32_t* docs, const i
     mtb_h2d(c, c->b_qgrp.p, grp.data(), 4ull * (ng + 1));
     return MT_OK;
 }
-static int mt_run_queries(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t* pos, const int32_t* ref,
-                          const int32_t* cli, std::vector<MtQueryOut>& res, int kind = MT_QK_LOCAL) {
+#ifndef MTB_HAVE_QUERY
+// A backend whose pools the host addresses (the emulation) takes this plain loop over the groups;
+// the HIP backend defines its own over the kernel and MTB_HAVE_QUERY.
+static int mtb_launch_query(mt_ctx* c, const MtQueryCall& call, const MtQuery* q, const uint32_t* grp, MtQueryOut* out, uint32_t n_groups) {
+    for (uint32_t g = 0; g < n_groups; g++) {
+        MtScratch sc; MtEngFast e; e.bind(c->S, q[grp[g]].doc, &sc);
+        mt_query_run(e, c->S, call, q, grp[g], grp[g + 1], out);
+    }
+    return MT_OK;
+}
+#endif
+static int mt_run_queries(mt_ctx* c, const MtQueryCall& call, uint32_t n, const uint32_t* docs, const int32_t* pos,
+                          const int32_t* ref, const int32_t* cli, std::vector<MtQueryOut>& res, int kind = MT_QK_LOCAL) {
     res.assign(n, MtQueryOut{});
     if (n == 0) return MT_OK;
     std::vector<uint32_t> ord;
@@ -1242,7 +1256,7 @@ static int mt_run_queries(mt_ctx* c, uint32_t n, const uint32_t* docs, const int
     int rc;
     if ((rc = mt_stage_queries(c, n, docs, pos, ref, cli, kind, ord, q, ng))) return rc;
     if ((rc = mtb_ensure(c, c->b_qout, sizeof(MtQueryOut) * n))) return rc;
-    if ((rc = mtb_launch_query(c, (const MtQuery*)c->b_q.p, (const uint32_t*)c->b_qgrp.p, (MtQueryOut*)c->b_qout.p, ng))) return rc;
+    if ((rc = mtb_launch_query(c, call, (const MtQuery*)c->b_q.p, (const uint32_t*)c->b_qgrp.p, (MtQueryOut*)c->b_qout.p, ng))) return rc;
     if ((rc = mtb_sync(c))) return rc;
     std::vector<MtQueryOut> tmp(n);
     mtb_d2h(c, tmp.data(), c->b_qout.p, sizeof(MtQueryOut) * n);
@@ -1304,15 +1318,15 @@ int MT_FN(get_containing_segment)(mt_ctx* c, uint32_t n, const uint32_t* docs, c
                                   const int32_t* cli, mt_seg_info* out, const char** json_arena, const uint64_t** json_off) {
     if (!c || (n && (!docs || !pos))) return MT_E_INVALID;
     std::vector<MtQueryOut> res;
-    int rc = mt_run_queries(c, n, docs, pos, ref, cli, res);
+    int rc = mt_run_queries(c, MtQueryCall{}, n, docs, pos, ref, cli, res);
     if (rc) return rc;
     if (out) for (uint32_t i = 0; i < n; i++) out[i] = res[i].info;
     return mt_seg_json(c, n, res, json_arena, json_off);
 }
 
-// Tile search (mt_query.h): the labels' match arrays go to the device and into MtState, where
+// Tile search (mt_query.h): the labels' match arrays go to the device and into the call, where
 // the query kernel's tile kinds read them.
-static int mt_tile_setup(mt_ctx* c, const mt_tile_labels* T, uint32_t n, const uint32_t* label) {
+static int mt_tile_setup(mt_ctx* c, const mt_tile_labels* T, uint32_t n, const uint32_t* label, MtQueryCall& call) {
     if (!T || (T->n_labels && T->n_values && !T->match)) { c->err = "tile labels missing"; return MT_E_INVALID; }
     if (T->n_values != c->names.value_json.size()) { c->err = "tile labels: n_values differs from the uploaded prop table"; return MT_E_INVALID; }
     if (T->n_labels >= (uint32_t)MT_QT_PRECEDING) { c->err = "too many tile labels"; return MT_E_INVALID; }
@@ -1322,8 +1336,7 @@ static int mt_tile_setup(mt_ctx* c, const mt_tile_labels* T, uint32_t n, const u
     if ((rc = mtb_ensure(c, c->b_tmatch, bytes + 1))) return rc;
     if ((rc = mtb_sync(c))) return rc;
     if (bytes) mtb_h2d(c, c->b_tmatch.p, T->match, bytes);
-    c->S.t_match = (const uint8_t*)c->b_tmatch.p; c->S.t_key = T->key; c->S.t_nvalues = T->n_values;
-    c->S.t_out = nullptr; c->S.t_cap = 0;
+    call.match = (const uint8_t*)c->b_tmatch.p; call.key = T->key; call.nvalues = T->n_values;
     return MT_OK;
 }
 
@@ -1333,12 +1346,13 @@ int MT_FN(find_tile)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t*
     if (!c || (n && (!docs || !pos || !label))) return MT_E_INVALID;
     for (uint32_t i = 0; i < n; i++)
         if (pos[i] < 0 && pos[i] != MT_POS_UNDEFINED) { c->err = "findTile: negative start position"; return MT_E_INVALID; }
-    int rc = mt_tile_setup(c, labels, n, label);
+    MtQueryCall call{};
+    int rc = mt_tile_setup(c, labels, n, label, call);
     if (rc) return rc;
     std::vector<int32_t> arg(n);
     for (uint32_t i = 0; i < n; i++) arg[i] = (int32_t)label[i] | ((flags && (flags[i] & MT_TILE_PRECEDING)) ? MT_QT_PRECEDING : 0);
     std::vector<MtQueryOut> res;
-    if ((rc = mt_run_queries(c, n, docs, pos, nullptr, arg.data(), res, MT_QK_TILE))) return rc;
+    if ((rc = mt_run_queries(c, call, n, docs, pos, nullptr, arg.data(), res, MT_QK_TILE))) return rc;
     if (out) for (uint32_t i = 0; i < n; i++) out[i] = res[i].info;
     return mt_seg_json(c, n, res, json_arena, json_off);
 }
@@ -1346,13 +1360,14 @@ int MT_FN(find_tile)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t*
 int MT_FN(tile_index)(mt_ctx* c, uint32_t n, const uint32_t* docs, const uint32_t* label, const mt_tile_labels* labels,
                       const mt_tile_rec** recs, const uint64_t** rec_off) {
     if (!c || !recs || !rec_off || (n && (!docs || !label))) return MT_E_INVALID;
-    int rc = mt_tile_setup(c, labels, n, label);
+    MtQueryCall call{};
+    int rc = mt_tile_setup(c, labels, n, label, call);
     if (rc) return rc;
     // two passes over the same scan, as mt_pack_size / mt_pack_doc: count, then fill at the
     // offsets the counts give
     std::vector<int32_t> at(n, 0), arg(label, label + n);
     std::vector<MtQueryOut> res;
-    if ((rc = mt_run_queries(c, n, docs, at.data(), nullptr, arg.data(), res, MT_QK_TILE_COUNT))) return rc;
+    if ((rc = mt_run_queries(c, call, n, docs, at.data(), nullptr, arg.data(), res, MT_QK_TILE_COUNT))) return rc;
     c->tile_off.assign((size_t)n + 1, 0);
     for (uint32_t i = 0; i < n; i++) c->tile_off[i + 1] = c->tile_off[i] + (uint64_t)(uint32_t)res[i].info.found;
     const uint64_t total = c->tile_off[n];
@@ -1360,11 +1375,9 @@ int MT_FN(tile_index)(mt_ctx* c, uint32_t n, const uint32_t* docs, const uint32_
     c->tile_recs.assign((size_t)total, mt_tile_rec{});
     if (total) {
         if ((rc = mtb_ensure(c, c->b_tout, sizeof(mt_tile_rec) * total))) return rc;
-        c->S.t_out = (mt_tile_rec*)c->b_tout.p; c->S.t_cap = total;
+        call.tiles = (mt_tile_rec*)c->b_tout.p; call.tile_cap = total;
         for (uint32_t i = 0; i < n; i++) at[i] = (int32_t)(uint32_t)c->tile_off[i];
-        rc = mt_run_queries(c, n, docs, at.data(), nullptr, arg.data(), res, MT_QK_TILE_FILL);
-        c->S.t_out = nullptr; c->S.t_cap = 0;
-        if (rc) return rc;
+        if ((rc = mt_run_queries(c, call, n, docs, at.data(), nullptr, arg.data(), res, MT_QK_TILE_FILL))) return rc;
         for (uint32_t i = 0; i < n; i++)
             if ((uint64_t)(uint32_t)res[i].info.found != c->tile_off[i + 1] - c->tile_off[i]) { c->err = "tile index: the passes disagree"; return MT_E_INVALID; }
         mtb_d2h(c, c->tile_recs.data(), c->b_tout.p, sizeof(mt_tile_rec) * total);
@@ -1379,14 +1392,15 @@ int MT_FN(tile_index)(mt_ctx* c, uint32_t n, const uint32_t* docs, const uint32_
 // once per pass (the fill's carry the offsets the counts gave: off[i] for query i's answer, and the
 // same for a walk's text), each pass one launch of the query kernel, with `count_kind` and then the
 // fill kind below it.  The kernel's answer records are not used by the range kinds, so none is
-// allocated or downloaded.  call: a walk's MtWalkCall (it lives in device memory, reached through
-// x_walk: MtState does not grow, mt_core.h), whose fill writes records to b_wout and text to
-// b_wtext; null for a text range, whose fill writes its units to b_xout.  total / ttotal: the
-// answers' and the walk's text's lengths.  Every return path clears what it set in MtState.
-static int mt_range_passes(mt_ctx* c, const std::string& what, const char* capped, uint32_t n, const uint32_t* docs,
-                           const int32_t* start, const int32_t* end, const int32_t* ref, const int32_t* cli, int count_kind,
-                           MtWalkCall* call, uint64_t* off, uint64_t& total, uint64_t& ttotal) {
+// allocated or downloaded.  call: the entry point's record, which has the placeholder or the walk's
+// flags and here gains the query records and the fill's outputs: a walk's records in b_wout and its
+// text in b_wtext, a text range's units in b_xout.  total / ttotal: the answers' and the walk's
+// text's lengths.
+static int mt_range_passes(mt_ctx* c, MtQueryCall& call, const std::string& what, const char* capped, uint32_t n,
+                           const uint32_t* docs, const int32_t* start, const int32_t* end, const int32_t* ref, const int32_t* cli,
+                           int count_kind, uint64_t* off, uint64_t& total, uint64_t& ttotal) {
     if (n > 0x7FFFFFFFu) { c->err = what + ": too many queries"; return MT_E_INVALID; }
+    const bool walk = count_kind == MT_QK_WALK_COUNT;
     std::vector<MtRangeQ> x(n, MtRangeQ{});
     for (uint32_t i = 0; i < n; i++) {
         x[i].start = start ? start[i] : 0; x[i].end = end ? end[i] : MT_POS_UNDEFINED;
@@ -1398,41 +1412,36 @@ static int mt_range_passes(mt_ctx* c, const std::string& what, const char* cappe
     int rc;
     if ((rc = mt_stage_queries(c, n, docs, nullptr, nullptr, nullptr, count_kind, ord, q, ng))) return rc;
     if ((rc = mtb_ensure(c, c->b_xq, sizeof(MtRangeQ) * n))) return rc;
-    if (call && (rc = mtb_ensure(c, c->b_wcall, sizeof(MtWalkCall)))) return rc;
-    auto done = [&](int r) { c->S.x_q = nullptr; c->S.x_nq = 0; c->S.x_out = nullptr; c->S.x_cap = 0; return r; };
-    auto pass = [&](std::vector<MtRangeQ>& y) {     // the records and the call up, one launch, the records down to y
+    auto pass = [&](std::vector<MtRangeQ>& y) {     // the records up, one launch, the records down to y
         mtb_h2d(c, c->b_xq.p, x.data(), sizeof(MtRangeQ) * n);
-        if (call) mtb_h2d(c, c->b_wcall.p, call, sizeof *call);
-        int r = mtb_launch_query(c, (const MtQuery*)c->b_q.p, (const uint32_t*)c->b_qgrp.p, (MtQueryOut*)c->b_qout.p, ng);
+        int r = mtb_launch_query(c, call, (const MtQuery*)c->b_q.p, (const uint32_t*)c->b_qgrp.p, (MtQueryOut*)c->b_qout.p, ng);
         if (!r) r = mtb_sync(c);
         if (!r) mtb_d2h(c, y.data(), c->b_xq.p, sizeof(MtRangeQ) * n);
         return r;
     };
-    done(MT_OK);
-    if (call) { call->q = (MtRangeQ*)c->b_xq.p; call->nq = n; c->S.x_walk = (const MtWalkCall*)c->b_wcall.p; }
-    else { c->S.x_q = (MtRangeQ*)c->b_xq.p; c->S.x_nq = n; }
-    if ((rc = pass(x))) return done(rc);
+    call.q = (MtRangeQ*)c->b_xq.p; call.nq = n;
+    if ((rc = pass(x))) return rc;
     total = ttotal = 0;
     for (uint32_t i = 0; i < n; i++) {
         x[i].at = total; x[i].tat = ttotal; off[i] = total;
         total += x[i].count; ttotal += x[i].tcount;
-        if (total > 0x80000000ull || ttotal > 0x80000000ull) { c->err = what + capped; return done(MT_E_INVALID); }
+        if (total > 0x80000000ull || ttotal > 0x80000000ull) { c->err = what + capped; return MT_E_INVALID; }
     }
     off[n] = total;
-    if (!total) return done(MT_OK);
-    const uint64_t units = call ? ttotal : total;
-    mt_ctx::DevBuf& arena = call ? c->b_wtext : c->b_xout;
-    if (call && (rc = mtb_ensure(c, c->b_wout, sizeof(mt_walk_rec) * total))) return done(rc);
-    if (units && (rc = mtb_ensure(c, arena, 2ull * units))) return done(rc);
-    if (call) { call->out = (mt_walk_rec*)c->b_wout.p; call->cap = total; }
-    if (units) { c->S.x_out = (uint16_t*)arena.p; c->S.x_cap = units; }
+    if (!total) return MT_OK;
+    const uint64_t units = walk ? ttotal : total;
+    mt_ctx::DevBuf& arena = walk ? c->b_wtext : c->b_xout;
+    if (walk && (rc = mtb_ensure(c, c->b_wout, sizeof(mt_walk_rec) * total))) return rc;
+    if (units && (rc = mtb_ensure(c, arena, 2ull * units))) return rc;
+    if (walk) { call.recs = (mt_walk_rec*)c->b_wout.p; call.rec_cap = total; }
+    if (units) { call.text = (uint16_t*)arena.p; call.text_cap = units; }
     for (uint32_t k = 0; k < n; k++) q[k].ref = count_kind - 1;
     mtb_h2d(c, c->b_q.p, q.data(), sizeof(MtQuery) * n);
     std::vector<MtRangeQ> y(n);
-    if ((rc = pass(y))) return done(rc);
+    if ((rc = pass(y))) return rc;
     for (uint32_t i = 0; i < n; i++)
-        if (y[i].filled != x[i].count || y[i].tfilled != x[i].tcount) { c->err = what + ": the passes disagree"; return done(MT_E_INVALID); }
-    return done(MT_OK);
+        if (y[i].filled != x[i].count || y[i].tfilled != x[i].tcount) { c->err = what + ": the passes disagree"; return MT_E_INVALID; }
+    return MT_OK;
 }
 static_assert(MT_QK_TEXT_FILL == MT_QK_TEXT_COUNT - 1 && MT_QK_WALK_FILL == MT_QK_WALK_COUNT - 1, "a fill kind lies below its count kind");
 
@@ -1446,14 +1455,15 @@ int MT_FN(get_text_range)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int
     c->range_arena.clear();
     *arena = c->range_arena.data(); *off = c->range_off.data();
     if (n == 0) return MT_OK;
-    c->S.x_phlen = placeholder_len;
+    MtQueryCall call{};
+    call.phlen = placeholder_len;
     for (uint32_t k = 0; k < MT_TEXT_PLACEHOLDER_MAX / 2; k++) {
         const uint32_t a = 2 * k < placeholder_len ? placeholder[2 * k] : 0u, b = 2 * k + 1 < placeholder_len ? placeholder[2 * k + 1] : 0u;
-        c->S.x_ph[k] = a | (b << 16);
+        call.ph[k] = a | (b << 16);
     }
     uint64_t total = 0, ttotal = 0;
-    const int rc = mt_range_passes(c, "text range", ": the answers hold more than 2^31 units; split the call", n, docs, start, end, ref,
-                                   cli, MT_QK_TEXT_COUNT, nullptr, c->range_off.data(), total, ttotal);
+    const int rc = mt_range_passes(c, call, "text range", ": the answers hold more than 2^31 units; split the call", n, docs, start, end,
+                                   ref, cli, MT_QK_TEXT_COUNT, c->range_off.data(), total, ttotal);
     if (rc) return rc;
     c->range_arena.resize((size_t)total);
     if (total) mtb_d2h(c, c->range_arena.data(), c->b_xout.p, 2ull * total);
@@ -1463,7 +1473,7 @@ int MT_FN(get_text_range)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int
 
 // Segment walks: the walk's records and text come down once.  Then the distinct (document,
 // prop_set) pairs the records name are fetched by one more launch of the query kernel (MT_QK_PSET
-// copies a map's chunks, packed, into a buffer the call's MtWalkCall names) and written out once each.
+// copies a map's chunks, packed, into a buffer the call names) and written out once each.
 int MT_FN(walk_segments)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int32_t* start, const int32_t* end,
                          const int32_t* ref, const int32_t* cli, uint32_t flags, const mt_walk_rec** recs, const uint64_t** rec_off,
                          const uint16_t** text_arena, const mt_walk_maps** maps) {
@@ -1489,12 +1499,12 @@ int MT_FN(walk_segments)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int3
     for (uint32_t i = 0; i < n; i++)
         for (const int32_t v : {start ? start[i] : 0, end ? end[i] : 0})
             if (v != MT_POS_UNDEFINED && (v < -(1 << 30) || v > (1 << 30))) { c->err = "walk: start / end outside [-2^30, 2^30]"; return MT_E_INVALID; }
-    MtWalkCall call{};
+    MtQueryCall call{};
     call.flags = text ? MT_WALK_TEXT : 0u;
     auto fail = [&](int r) { c->walk_off.assign((size_t)n + 1, 0); return r; };
     uint64_t total = 0, ttotal = 0;
-    int rc = mt_range_passes(c, "walk", ": the answers hold more than 2^31 records or text units; split the call", n, docs, start, end,
-                             ref, cli, MT_QK_WALK_COUNT, &call, c->walk_off.data(), total, ttotal);
+    int rc = mt_range_passes(c, call, "walk", ": the answers hold more than 2^31 records or text units; split the call", n, docs, start,
+                             end, ref, cli, MT_QK_WALK_COUNT, c->walk_off.data(), total, ttotal);
     if (rc) return fail(rc);
     if (!total) return MT_OK;
     c->walk_recs.resize((size_t)total);
@@ -1529,12 +1539,9 @@ int MT_FN(walk_segments)(mt_ctx* c, uint32_t n, const uint32_t* docs, const int3
         uint32_t ng = 0;
         if ((rc = mt_stage_queries(c, m, c->walk_map_doc.data(), mpos.data(), nullptr, mat.data(), MT_QK_PSET, ord, q, ng))) return fail(rc);
         if ((rc = mtb_ensure(c, c->b_wmaps, sizeof(MtPSet) * chunks))) return fail(rc);
-        call.out = nullptr; call.cap = 0; call.maps = (MtPSet*)c->b_wmaps.p; call.mcap = chunks;
-        mtb_h2d(c, c->b_wcall.p, &call, sizeof call);
-        c->S.x_walk = (const MtWalkCall*)c->b_wcall.p;
-        rc = mtb_launch_query(c, (const MtQuery*)c->b_q.p, (const uint32_t*)c->b_qgrp.p, (MtQueryOut*)c->b_qout.p, ng);
+        call.maps = (MtPSet*)c->b_wmaps.p; call.map_cap = chunks;
+        rc = mtb_launch_query(c, call, (const MtQuery*)c->b_q.p, (const uint32_t*)c->b_qgrp.p, (MtQueryOut*)c->b_qout.p, ng);
         if (!rc) rc = mtb_sync(c);
-        c->S.x_q = nullptr;
         if (rc) return fail(rc);
         std::vector<MtPSet> got((size_t)chunks);
         mtb_d2h(c, got.data(), c->b_wmaps.p, sizeof(MtPSet) * chunks);
@@ -1557,7 +1564,7 @@ int MT_FN(resolve_remote_position)(mt_ctx* c, uint32_t n, const uint32_t* docs, 
                                    const int32_t* cli, int32_t* out) {
     if (!c || (n && (!docs || !pos || !out))) return MT_E_INVALID;
     std::vector<MtQueryOut> res;
-    int rc = mt_run_queries(c, n, docs, pos, ref, cli, res);
+    int rc = mt_run_queries(c, MtQueryCall{}, n, docs, pos, ref, cli, res);
     if (rc) return rc;
     for (uint32_t i = 0; i < n; i++) out[i] = res[i].info.resolved;
     return MT_OK;

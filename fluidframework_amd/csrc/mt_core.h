@@ -310,40 +310,14 @@ struct MtState {                              // device pools, doc-major
     // and MT_VINFO_SEQM1; element -1: incr of a fresh consensus object (null: combine sets
     // unsupported); mt_set_props
     const int32_t* p_vinfo;
-    // tile search (mt_query.h; set per call by mt_find_tile / mt_tile_index): the labels' match
-    // arrays ([label * t_nvalues + value id]), the key id of "referenceTileLabels", and the
-    // index's record array (t_cap records)
-    const uint8_t* t_match; uint32_t t_key, t_nvalues;
-    mt_tile_rec* t_out; unsigned long long t_cap;
-    // the range queries (mt_query.h: two visitors of one scan; set per call, by one two-pass driver
-    // that also clears what it set, mt_api_impl.h).  A text range (mt_get_text_range): the call's
-    // query records (MtRangeQ; MtQuery::pos indexes them), the placeholder a marker stands for
-    // (x_phlen <= 16 UTF-16 units, two a word) and the fill pass's output arena (x_cap units).
-    // A segment walk (mt_walk_segments) adds nothing here: MtState is an argument of every kernel,
-    // the replay kernels included, and does not grow for a cold path.  A walk's state lives in a
-    // MtWalkCall in device memory, and during its launches this one pointer names it as x_walk,
-    // with x_nq == 0, so a text kind finds no record; x_out / x_cap are then the walk's text arena.
-    // Only one of the two calls is under way at a time, and each clears the pointer when it ends.
-    union { struct MtRangeQ* x_q; const struct MtWalkCall* x_walk; };
-    uint32_t x_nq, x_phlen;
-    uint32_t x_ph[MT_TEXT_PLACEHOLDER_MAX / 2];
-    uint16_t* x_out; unsigned long long x_cap;
+    // A query call's arguments are not here: the query kernel takes them as an argument of its own
+    // (MtQueryCall, mt_query.h).
+    // The size is pinned (profiles/query_call/README.md): at 224 bytes the replay and generate
+    // kernels compile to what they were when the query arguments lay here; at 216 the hot replay
+    // kernel does not (kernel_resources_216_bytes_hot_kernel.txt there).
+    unsigned long long pad;
 };
-// One mt_walk_segments call: its query records (MtQuery::pos indexes them), MT_WALK_* flags, the
-// fill pass's record array (cap records), and where MT_QK_PSET copies the distinct property maps,
-// chunk by chunk (mcap chunks).
-struct __attribute__((aligned(16))) MtWalkCall {
-    struct MtRangeQ* q; uint32_t nq, flags;
-    mt_walk_rec* out; unsigned long long cap;
-    MtPSet* maps; unsigned long long mcap;
-};
-// One range query, a text range or a segment walk: the range and the view as the caller gave them,
-// where the answer goes (a text range's units, a walk's records), what the count pass found and
-// what the fill pass wrote; the same three for a walk's text, which a text range leaves zero.
-struct __attribute__((aligned(16))) MtRangeQ {
-    int32_t start, end, ref, client;
-    unsigned long long at, count, filled, tat, tcount, tfilled;
-};
+static_assert(sizeof(MtState) == 224, "MtState's size is pinned: profiles/query_call/README.md");
 #define MT_VINFO_ID    0x3FFFFFFF
 #define MT_VINFO_NONE  0x3FFFFFFF
 #define MT_VINFO_SEQM1 0x40000000

@@ -45,14 +45,14 @@ struct mt_ctx {
            b_q, b_qgrp, b_qout, b_qat, b_qlen, b_qoff, b_qtext,   // position queries (mt_get_containing_segment)
            b_tmatch, b_tout,                                      // tile search: the labels' match arrays, the index's records
            b_xq, b_xout,                                          // range queries: the query records; text ranges: the fill pass's arena
-           b_wcall, b_wout, b_wtext, b_wmaps;                     // segment walks: the call, the fill pass's records and text, the maps' chunks
+           b_wout, b_wtext, b_wmaps;                              // segment walks: the fill pass's records and text, the maps' chunks
     DevBuf b_runs, b_batch;
     // Every device buffer above, for mt_destroy (one list beside the declarations).
     std::vector<DevBuf*> dev_bufs() {
         return {&b_stage, &b_pack_docs, &b_pack_sz, &b_pack_off, &b_gencl, &b_cursor, &b_doc, &b_off, &b_rec, &b_pay, &b_pbase,
                 &b_rel, &b_drec, &b_dcount, &b_pset_off, &b_pkey, &b_pval, &b_pfalsy, &b_pclass, &b_pkind, &b_tmp0, &b_tmp1,
                 &b_tmp2, &b_tmp3, &b_ld_meta, &b_ld_seg, &b_ld_pay, &b_ld_plan, &b_ld_poff, &b_dtext, &b_resume, &b_start, &b_q,
-                &b_qgrp, &b_qout, &b_qat, &b_qlen, &b_qoff, &b_qtext, &b_tmatch, &b_tout, &b_xq, &b_xout, &b_wcall, &b_wout, &b_wtext, &b_wmaps,
+                &b_qgrp, &b_qout, &b_qat, &b_qlen, &b_qoff, &b_qtext, &b_tmatch, &b_tout, &b_xq, &b_xout, &b_wout, &b_wtext, &b_wmaps,
                 &b_runs, &b_batch};
     }
     // options.mergeTreeSnapshotChunkSize per document (mt_set_doc_snapshot_chunk; 0 = 10,000)

@@ -46,13 +46,14 @@ __global__ __launch_bounds__(64) void mt_get_length_kernel(MtState S, const uint
     if (__lane_id() == 0) out[blockIdx.x] = l;
 }
 
-// Position queries (mt_query.h): one wave per document group of the sorted queries.
-__global__ __launch_bounds__(64) void mt_query_kernel(MtState S, const MtQuery* q, const uint32_t* grp, MtQueryOut* out) {
+// Queries (mt_query.h): one wave per document group of the sorted queries; the call's arguments
+// are the kernel's own (MtQueryCall), not MtState's.
+__global__ __launch_bounds__(64) void mt_query_kernel(MtState S, MtQueryCall call, const MtQuery* q, const uint32_t* grp, MtQueryOut* out) {
     __shared__ MtScratch sc;
     const uint32_t q0 = grp[blockIdx.x], q1 = grp[blockIdx.x + 1];
     MtEngFast e;
     e.bind(S, q[q0].doc, &sc);
-    mt_query_run(e, S, q, q0, q1, out);
+    mt_query_run(e, S, call, q, q0, q1, out);
 }
 // Text of found segments into one arena: workgroup i copies len[i] units from text[at[i]].
 __global__ __launch_bounds__(256) void mt_gather_text_kernel(const uint16_t* text, const unsigned long long* at,
@@ -274,8 +275,9 @@ static int mtb_launch_update_seq(mt_ctx* c, const uint32_t* docs, const int32_t*
 static int mtb_launch_get_length(mt_ctx* c, const uint32_t* docs, const int32_t* ref, const int32_t* cli, int32_t* out, uint32_t n) {
     return mtb_launch(c, mt_get_length_kernel, n, 64, c->S, docs, ref, cli, out);
 }
-static int mtb_launch_query(mt_ctx* c, const MtQuery* q, const uint32_t* grp, MtQueryOut* out, uint32_t n_groups) {
-    return mtb_launch(c, mt_query_kernel, n_groups, 64, c->S, q, grp, out);
+#define MTB_HAVE_QUERY 1
+static int mtb_launch_query(mt_ctx* c, const MtQueryCall& call, const MtQuery* q, const uint32_t* grp, MtQueryOut* out, uint32_t n_groups) {
+    return mtb_launch(c, mt_query_kernel, n_groups, 64, c->S, call, q, grp, out);
 }
 static int mtb_launch_gather_text(mt_ctx* c, const unsigned long long* at, const uint32_t* len, const unsigned long long* off,
                                   uint16_t* dst, uint32_t n) {

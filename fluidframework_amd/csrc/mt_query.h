@@ -27,15 +27,14 @@
 #define MT_QK_TILE (-2)
 #define MT_QK_TILE_COUNT (-3)
 #define MT_QK_TILE_FILL (-4)
-// a text range (mt_get_text_range): pos is the query's record (MtRangeQ) in MtState::x_q, which
+// a text range (mt_get_text_range): pos is the query's record (MtRangeQ) in MtQueryCall::q, which
 // holds the range and the view; the count pass and the fill pass of the same scan
 #define MT_QK_TEXT_COUNT (-5)
 #define MT_QK_TEXT_FILL (-6)
-// a segment walk (mt_walk_segments): pos is the query's record in the call's MtWalkCall, which
-// MtState::x_walk names while the walk's launches run (mt_core.h); the count pass and
-// the fill pass of the same scan.  MT_QK_PSET: pos is a property-set id of the document, whose
-// chunks are copied to MtWalkCall::maps from chunk `client` on (the walk's distinct maps, fetched
-// after its fill; no answer record is written).
+// a segment walk (mt_walk_segments): pos is the query's record in MtQueryCall::q, as a text range's;
+// the count pass and the fill pass of the same scan.  MT_QK_PSET: pos is a property-set id of the
+// document, whose chunks are copied to MtQueryCall::maps from chunk `client` on (the walk's distinct
+// maps, fetched after its fill; no answer record is written).
 #define MT_QK_WALK_COUNT (-7)
 #define MT_QK_WALK_FILL (-8)
 #define MT_QK_PSET (-9)
@@ -49,6 +48,32 @@ struct __attribute__((aligned(16))) MtQueryOut {
     unsigned long long pad;
     MtPSet ps[MT_PKEYS / MT_PSK];
 };
+// One range query, a text range or a segment walk: the range and the view as the caller gave them,
+// where the answer goes (a text range's units, a walk's records), what the count pass found and
+// what the fill pass wrote; the same three for a walk's text, which a text range leaves zero.
+struct __attribute__((aligned(16))) MtRangeQ {
+    int32_t start, end, ref, client;
+    unsigned long long at, count, filled, tat, tcount, tfilled;
+};
+// What one launch of the query kernel needs beyond the pools: the kernel's second argument, by
+// value, built by the ABI's entry point on its stack.  A query's kind says which members it reads;
+// a member no kind of the launch reads stays zero.
+struct MtQueryCall {
+    // the tile kinds: the labels' match arrays ([label * nvalues + value id]), the key id of
+    // "referenceTileLabels", and the index's record array (MT_QK_TILE_FILL; tile_cap records)
+    const uint8_t* match; uint32_t key, nvalues;
+    mt_tile_rec* tiles; unsigned long long tile_cap;
+    // the range kinds: the query records (MtQuery::pos indexes them) and a walk's MT_WALK_* flags
+    MtRangeQ* q; uint32_t nq, flags;
+    // the placeholder a marker stands for in a text range (phlen <= 16 UTF-16 units, two a word)
+    uint32_t phlen, ph[MT_TEXT_PLACEHOLDER_MAX / 2];
+    // the fill passes' outputs: a text range's units or a walk's text (text_cap units), a walk's
+    // records (rec_cap records); where MT_QK_PSET copies the maps, chunk by chunk (map_cap chunks)
+    uint16_t* text; unsigned long long text_cap;
+    mt_walk_rec* recs; unsigned long long rec_cap;
+    MtPSet* maps; unsigned long long map_cap;
+};
+static_assert(sizeof(MtQueryCall) == 136, "MtQueryCall is 136 bytes of kernel arguments");
 static_assert(sizeof(mt_seg_info) == 64, "mt_seg_info is 16 dwords");
 static_assert(sizeof(mt_tile_rec) == 32, "mt_tile_rec is 8 dwords");
 static_assert(sizeof(mt_walk_rec) == 64, "mt_walk_rec is 16 dwords");
@@ -214,16 +239,16 @@ MT_HD void mt_tile_unit(Eng& e, const MtTileCursor& c, MtTileUnit& u) {
 // map tested and its result are remembered (wave-uniform).
 struct MtTileMemo { int lab, ps; bool res; };
 template <class Eng>
-MT_HD bool mt_tile_map_has(Eng& e, const MtState& S, int ps, int lab, MtTileMemo& memo) {
+MT_HD bool mt_tile_map_has(Eng& e, const MtQueryCall& call, int ps, int lab, MtTileMemo& memo) {
     if (ps < 0 || ps >= e.psetTop) return false;
     if (memo.ps == ps && memo.lab == lab) return memo.res;
     int n = uni(e.pset[ps].n);
     const int room = (e.psetTop - ps) * MT_PSK;
     n = n < 0 ? 0 : (n > MT_PKEYS ? MT_PKEYS : n);
     n = n > room ? room : n;
-    const int key = (int)S.t_key;
-    const uint32_t nv = S.t_nvalues;
-    const uint8_t* mrow = S.t_match + (size_t)lab * nv;
+    const int key = (int)call.key;
+    const uint32_t nv = call.nvalues;
+    const uint8_t* mrow = call.match + (size_t)lab * nv;
     bool res = false;
     for (int base = 0; base < n && !res; base += MT_WAVE) {
         const int m = (n - base) < MT_WAVE ? (n - base) : MT_WAVE;
@@ -295,7 +320,7 @@ MT_HD unsigned long long mt_tile_path(Eng& e, const MtTileCursor& c, const MtTil
 // findTile (the rule: include/mtgpu.h).  Returns the row (-1: undefined) with its observer
 // start, depth and path.
 template <class Eng>
-MT_HD int mt_find_tile_doc(Eng& e, const MtState& S, int pos, int lab, bool preceding, MtTileMemo& memo, int& op, int& depth,
+MT_HD int mt_find_tile_doc(Eng& e, const MtQueryCall& call, int pos, int lab, bool preceding, MtTileMemo& memo, int& op, int& depth,
                            unsigned long long& path) {
     if (!mt_tile_blk_ok(e, e.root)) return -1;
     const int L = uni(e.bk(e.root).len);
@@ -313,7 +338,7 @@ MT_HD int mt_find_tile_doc(Eng& e, const MtState& S, int pos, int lab, bool prec
             if (!mt_tile_next(e, c, -1, true)) return -1;
         }
         const int t = 63 - __builtin_clzll(u.present);
-        if (!((u.candAny >> t) & 1ull) || !mt_tile_map_has(e, S, wave_at(u.props, t), lab, memo)) return -1;
+        if (!((u.candAny >> t) & 1ull) || !mt_tile_map_has(e, call, wave_at(u.props, t), lab, memo)) return -1;
         op = c.base + wave_at(u.pre, t);
         path = mt_tile_path(e, c, u, t, depth);
         return wave_at(u.row, t);
@@ -334,7 +359,7 @@ MT_HD int mt_find_tile_doc(Eng& e, const MtState& S, int pos, int lab, bool prec
         while (m) {                                 // candidates nearest first
             const int t = dir < 0 ? 63 - __builtin_clzll(m) : __builtin_ctzll(m);
             m &= ~(1ull << t);
-            if (mt_tile_map_has(e, S, wave_at(u.props, t), lab, memo)) {
+            if (mt_tile_map_has(e, call, wave_at(u.props, t), lab, memo)) {
                 op = ub + wave_at(u.pre, t);
                 path = mt_tile_path(e, c, u, t, depth);
                 return wave_at(u.row, t);
@@ -347,7 +372,7 @@ MT_HD int mt_find_tile_doc(Eng& e, const MtState& S, int pos, int lab, bool prec
 // The tile index of one document: every visible matching tile in document order.  out null:
 // count only.  Returns the count; records go to out[0 .. count), as far as `room` reaches.
 template <class Eng>
-MT_HD int mt_tile_index_doc(Eng& e, const MtState& S, int lab, MtTileMemo& memo, mt_tile_rec* out, unsigned long long room) {
+MT_HD int mt_tile_index_doc(Eng& e, const MtQueryCall& call, int lab, MtTileMemo& memo, mt_tile_rec* out, unsigned long long room) {
     if (!mt_tile_blk_ok(e, e.root) || uni(e.bk(e.root).len) <= 0) return 0;
     MtTileCursor c; c.U = -1; c.lvl = 0; c.base = 0;
     MtTileUnit u;
@@ -359,7 +384,7 @@ MT_HD int mt_tile_index_doc(Eng& e, const MtState& S, int lab, MtTileMemo& memo,
         while (m) {
             const int t = __builtin_ctzll(m);
             m &= ~(1ull << t);
-            if (mt_tile_map_has(e, S, wave_at(u.props, t), lab, memo)) hit |= 1ull << t;
+            if (mt_tile_map_has(e, call, wave_at(u.props, t), lab, memo)) hit |= 1ull << t;
         }
         if (hit && out) {
             const int ub = c.base, tb = tbase, c0 = cnt;
@@ -506,7 +531,7 @@ MT_HD void mt_scan_copy(Eng& e, const LaneArr<int>& olen, const LaneArr<int>& op
 // to the range and a second scan over the output lengths.  out null: count only.  Returns the
 // answer's length; units go to out[0 .. length), as far as `room` reaches.
 template <class Eng>
-MT_HD unsigned long long mt_text_range_doc(Eng& e, const MtState& S, int start, int end, int ref, int qc, uint16_t* out,
+MT_HD unsigned long long mt_text_range_doc(Eng& e, const MtQueryCall& call, int start, int end, int ref, int qc, uint16_t* out,
                                            unsigned long long room) {
     if (!mt_tile_blk_ok(e, e.root)) return 0;
     const int E = end == (int)0x80000000 ? 0x7FFFFFFF : end;       // undefined: the view's length
@@ -517,7 +542,7 @@ MT_HD unsigned long long mt_text_range_doc(Eng& e, const MtState& S, int start, 
     if (swapped ? lo <= 0 : hi <= lo) return 0;
     int r, c;
     const bool local = mt_view_of(ref, qc, r, c);
-    const int plen = S.x_phlen > MT_TEXT_PLACEHOLDER_MAX ? MT_TEXT_PLACEHOLDER_MAX : (int)S.x_phlen;
+    const int plen = call.phlen > MT_TEXT_PLACEHOLDER_MAX ? MT_TEXT_PLACEHOLDER_MAX : (int)call.phlen;
     static_assert(MT_TEXT_PLACEHOLDER_MAX == 16, "the placeholder is picked from eight words");
     MtViewScan sc;
     MtScanUnit u;
@@ -544,7 +569,7 @@ MT_HD unsigned long long mt_text_range_doc(Eng& e, const MtState& S, int start, 
                 const bool marker = (own(u.q0, t).w & MT_M_MARKER) != 0;
                 return marker ? -1 : (int)own(u.q1, t).x + ((lo > p ? lo : p) - p);
             });
-            mt_scan_copy(e, olen, opre, T, src, (const int*)S.x_ph, out, done, room);
+            mt_scan_copy(e, olen, opre, T, src, (const int*)call.ph, out, done, room);
         }
         done += (unsigned long long)T;
     } while (!swapped && mt_scan_next(e, sc, u.vsum, hi));
@@ -564,7 +589,7 @@ MT_HD unsigned long long mt_text_range_doc(Eng& e, const MtState& S, int start, 
 // the records; tcount: the text units.  Stores reach rec[0 .. room) and txt[0 .. troom) only;
 // tat: where txt starts in the call's arena (a record's text_off is absolute).
 template <class Eng>
-MT_HD unsigned long long mt_walk_doc(Eng& e, const MtState& S, int start, int end, int ref, int qc, bool text, mt_walk_rec* rec,
+MT_HD unsigned long long mt_walk_doc(Eng& e, const MtQueryCall& call, int start, int end, int ref, int qc, bool text, mt_walk_rec* rec,
                                      unsigned long long room, uint16_t* txt, unsigned long long tat, unsigned long long troom,
                                      unsigned long long& tcount) {
     tcount = 0;
@@ -625,7 +650,7 @@ MT_HD unsigned long long mt_walk_doc(Eng& e, const MtState& S, int start, int en
         if (txt && T > 0) {
             // each row's first source unit: a visited text row's toff (no row asks for the placeholder)
             const auto src = wave_map(MT_WAVE, [&](int t) MT_LAM { return (int)own(u.q1, t).x; });
-            mt_scan_copy(e, olen, opre, T, src, (const int*)S.x_ph, txt, tdone, troom);
+            mt_scan_copy(e, olen, opre, T, src, (const int*)call.ph, txt, tdone, troom);
         }
         done += (unsigned long long)__builtin_popcountll(hit);
         tdone += (unsigned long long)T;
@@ -646,51 +671,37 @@ MT_HD void mt_query_pset(Eng& e, MtPSet* maps, unsigned long long mcap, int ps, 
 }
 
 template <class Eng>
-MT_HD void mt_query_run(Eng& e, const MtState& S, const MtQuery* q, uint32_t q0, uint32_t q1, MtQueryOut* out) {
+MT_HD void mt_query_run(Eng& e, const MtState& S, const MtQueryCall& call, const MtQuery* q, uint32_t q0, uint32_t q1, MtQueryOut* out) {
     MtTileMemo memo; memo.lab = -1; memo.ps = -1; memo.res = false;
     for (uint32_t i = q0; i < q1; i++) {
         const int pos = uni(q[i].pos), ref = uni(q[i].ref), qc = uni(q[i].client);
-        if (ref <= MT_QK_WALK_COUNT) {              // a segment walk: its record holds the query and takes the counts
-            const MtWalkCall* wc = S.x_walk;
-            if (!wc) continue;
-            if (ref == MT_QK_PSET) {
-                mt_query_pset(e, (MtPSet*)uni64((unsigned long long)wc->maps), uni64(wc->mcap), pos, qc);
+        if (ref == MT_QK_PSET) { mt_query_pset(e, call.maps, call.map_cap, pos, qc); continue; }
+        if (ref <= MT_QK_TEXT_COUNT) {              // a range kind: its record holds the query and takes the counts
+            if (!call.q || (uint32_t)pos >= call.nq) continue;
+            MtRangeQ* xp = &call.q[(uint32_t)pos];
+            const bool walk = ref <= MT_QK_WALK_COUNT, fill = ref == MT_QK_WALK_FILL || ref == MT_QK_TEXT_FILL;
+            const bool text = !walk || (call.flags & MT_WALK_TEXT) != 0;
+            const unsigned long long at = uni64(xp->at), cap = uni64(xp->count);
+            // the text: a text range's answer, at `at`; a walk's rows' texts, at the record's tat
+            const unsigned long long tat = walk ? uni64(xp->tat) : at, tcap = walk ? uni64(xp->tcount) : cap;
+            unsigned long long troom = (fill && text && call.text && tat < call.text_cap) ? call.text_cap - tat : 0ull;
+            troom = troom < tcap ? troom : tcap;
+            uint16_t* txt = troom ? call.text + tat : nullptr;
+            if (!walk) {
+                const unsigned long long cnt = mt_text_range_doc(e, call, uni(xp->start), uni(xp->end), uni(xp->ref), uni(xp->client),
+                                                                 txt, troom);
+                wave_for(1, [&](int) MT_LAM { if (fill) xp->filled = cnt; else xp->count = cnt; });
+                wave_sync();
                 continue;
             }
-            const bool fill = ref == MT_QK_WALK_FILL;
-            MtRangeQ* wq = (MtRangeQ*)uni64((unsigned long long)wc->q);
-            mt_walk_rec* wout = (mt_walk_rec*)uni64((unsigned long long)wc->out);
-            const unsigned long long wcap = uni64(wc->cap);
-            if (!wq || (uint32_t)pos >= uni(wc->nq)) continue;
-            MtRangeQ& x = wq[(uint32_t)pos];
-            const bool text = (uni(wc->flags) & MT_WALK_TEXT) != 0;
-            const unsigned long long at = uni64(x.at), cap = uni64(x.count), tat = uni64(x.tat), tcap = uni64(x.tcount);
-            unsigned long long room = (fill && wout && at < wcap) ? wcap - at : 0ull;
+            unsigned long long room = (fill && call.recs && at < call.rec_cap) ? call.rec_cap - at : 0ull;
             room = room < cap ? room : cap;
-            unsigned long long troom = (fill && text && S.x_out && tat < S.x_cap) ? S.x_cap - tat : 0ull;
-            troom = troom < tcap ? troom : tcap;
             unsigned long long tcnt = 0;
-            const unsigned long long cnt = mt_walk_doc(e, S, uni(x.start), uni(x.end), uni(x.ref), uni(x.client), text,
-                                                       room ? wout + at : nullptr, room, troom ? S.x_out + tat : nullptr, tat,
-                                                       troom, tcnt);
-            MtRangeQ* xp = &x;
+            const unsigned long long cnt = mt_walk_doc(e, call, uni(xp->start), uni(xp->end), uni(xp->ref), uni(xp->client), text,
+                                                       room ? call.recs + at : nullptr, room, txt, tat, troom, tcnt);
             wave_for(1, [&](int) MT_LAM {
                 if (fill) { xp->filled = cnt; xp->tfilled = tcnt; } else { xp->count = cnt; xp->tcount = tcnt; }
             });
-            wave_sync();
-            continue;
-        }
-        if (ref <= MT_QK_TEXT_COUNT) {              // a text range: its record holds the query and takes the count
-            const bool fill = ref == MT_QK_TEXT_FILL;
-            if (!S.x_q || (uint32_t)pos >= S.x_nq) continue;
-            MtRangeQ& x = S.x_q[(uint32_t)pos];
-            const unsigned long long at = uni64(x.at), cap = uni64(x.count);
-            unsigned long long room = (fill && S.x_out && at < S.x_cap) ? S.x_cap - at : 0ull;
-            room = room < cap ? room : cap;
-            const unsigned long long cnt = mt_text_range_doc(e, S, uni(x.start), uni(x.end), uni(x.ref), uni(x.client),
-                                                             room ? S.x_out + at : nullptr, room);
-            MtRangeQ* xp = &x;
-            wave_for(1, [&](int) MT_LAM { if (fill) xp->filled = cnt; else xp->count = cnt; });
             wave_sync();
             continue;
         }
@@ -699,13 +710,13 @@ MT_HD void mt_query_run(Eng& e, const MtState& S, const MtQuery* q, uint32_t q0,
             if (ref == MT_QK_TILE) {
                 int op = 0, depth = 0;
                 unsigned long long path = 0;
-                const int s = mt_find_tile_doc(e, S, pos, lab, (qc & MT_QT_PRECEDING) != 0, memo, op, depth, path);
+                const int s = mt_find_tile_doc(e, call, pos, lab, (qc & MT_QT_PRECEDING) != 0, memo, op, depth, path);
                 mt_query_emit(e, S, out[i], s, 0, op, depth, path, (int)0x80000000);
             } else {
                 const bool fill = ref == MT_QK_TILE_FILL;
                 const unsigned long long at = fill ? (unsigned long long)(uint32_t)pos : 0ull;
-                const unsigned long long room = (fill && S.t_out && at < S.t_cap) ? S.t_cap - at : 0ull;
-                const int cnt = mt_tile_index_doc(e, S, lab, memo, room ? S.t_out + at : nullptr, room);
+                const unsigned long long room = (fill && call.tiles && at < call.tile_cap) ? call.tile_cap - at : 0ull;
+                const int cnt = mt_tile_index_doc(e, call, lab, memo, room ? call.tiles + at : nullptr, room);
                 MtQueryOut& o = out[i];
                 wave_for(16, [&](int k) MT_LAM { ((int*)&o.info)[k] = k == 0 ? cnt : 0; });
                 wave_sync();
@@ -727,4 +738,11 @@ MT_HD void mt_query_run(Eng& e, const MtState& S, const MtQuery* q, uint32_t q0,
         }
         mt_query_emit(e, S, out[i], s, off, op, depth, path, resolved);
     }
+}
+// The form without a record, as backend sources written before MtQueryCall call it: only position
+// queries are answered (they read no member of the record; every other kind finds none).
+template <class Eng>
+[[deprecated("pass the call's MtQueryCall")]] MT_HD void mt_query_run(Eng& e, const MtState& S, const MtQuery* q, uint32_t q0,
+                                                                      uint32_t q1, MtQueryOut* out) {
+    mt_query_run(e, S, MtQueryCall{}, q, q0, q1, out);
 }

@@ -12,6 +12,8 @@ warm-up calls, one process.  Prints one JSON line:
   (e) mt_get_containing_segment with JSON, one query per segment start of the same documents
       (the starts are (a)'s records): the only per-segment path there was
   (f) mt_get_text_range of (a)'s and of (c)'s ranges: a floor for the text part
+  (g) mt_tile_index of the same documents, label "pg"; (h) mt_get_text of them, its yardstick;
+      (i) mt_find_tile, one query per document, no JSON ("Tile search")
 and the ratios e / a, a / f_whole, c / f_paragraphs.
 usage: python tools/walk_measure.py [--docs 4096] [--emu] [--out FILE]
 """
@@ -135,6 +137,28 @@ def main():
     # (f) mt_get_text_range of the same ranges
     res["f_text_range_whole_ms"] = fw = timed(eng, lambda: text_range(docs, None, None))
     res["f_text_range_paragraphs_ms"] = fp = timed(eng, lambda: text_range(qd, qs, qe))
+    # (g)-(i) the tile search's figures on the same documents
+    lab = np.zeros(N, np.uint32)
+    labels = eng._tile_labels("pg")
+    tr, to = P(), P()
+
+    def tile_index():
+        rc = fn["tile_index"](h, N, docs.ctypes.data, lab.ctypes.data, ctypes.byref(labels), ctypes.byref(tr), ctypes.byref(to))
+        assert rc == 0, rc
+        return int(ctypes.cast(to, ctypes.POINTER(ctypes.c_uint64))[N])
+    assert tile_index() == N * len(trecs)
+    res["g_tile_index_ms"] = timed(eng, tile_index)
+    res["g_records"] = N * len(trecs)
+    res["h_get_text_ms"] = timed(eng, lambda: fn["get_text"](h, N, docs.ctypes.data, ctypes.byref(arena), ctypes.byref(off)))
+    tpos, tfl, tinfo = np.full(N, len(whole) // 2, np.int32), np.ones(N, np.uint8), np.zeros(N * 16, np.int32)
+
+    def find_tile():
+        rc = fn["find_tile"](h, N, docs.ctypes.data, tpos.ctypes.data, tfl.ctypes.data, lab.ctypes.data, ctypes.byref(labels),
+                             tinfo.ctypes.data, None, None)
+        assert rc == 0, rc
+    find_tile()
+    assert (tinfo.reshape(-1, 16)[:, 0] == 1).all()
+    res["i_find_tile_ms"] = timed(eng, find_tile)
     res["ratio_e_over_a"] = round(e["median"] / a["median"], 2)
     res["ratio_a_over_f_whole"] = round(a["median"] / fw["median"], 2)
     res["ratio_c_over_f_paragraphs"] = round(c["median"] / fp["median"], 2)
