@@ -131,7 +131,7 @@ enum { MT_BIGF_NO_BCACHE = 1, MT_BIGF_NO_PREFETCH = 2, MT_BIGF_NO_TABLE = 4, MT_
 enum { MT_RES_HBM = 0, MT_RES_LDS = 1, MT_RES_BLK = 2, MT_RES_BIG = 3, MT_RES_BLKW = 4 };
 // Diagnostic builds keep per-document phase/event counters (prof[]) across binds;
 // product builds never load or store them (8 SGPR pairs fewer live in the replay loop).
-#if defined(MT_PROFILE) || defined(MT_PROFILE2) || defined(MT_PROFILE3) || defined(MT_PROFILE4) || defined(MT_BPC_STATS) || defined(MT_EVCOUNT3) || defined(MT_EVCOUNT) || defined(MT_EVCOUNT2) || defined(MT_EVRANGE)
+#if defined(MT_PROFILE) || defined(MT_PROFILE2) || defined(MT_PROFILE3) || defined(MT_PROFILE4) || defined(MT_BPC_STATS) || defined(MT_EVCOUNT3) || defined(MT_EVCOUNT) || defined(MT_EVCOUNT2) || defined(MT_EVRANGE) || defined(MT_EVGATHER)
 #define MT_KEEP_PROF 1
 #else
 #define MT_KEEP_PROF 0
@@ -159,6 +159,21 @@ enum { MT_RES_HBM = 0, MT_RES_LDS = 1, MT_RES_BLK = 2, MT_RES_BIG = 3, MT_RES_BL
 #define MT_EV2(i, v) prof[i] += (unsigned long long)(v)
 #else
 #define MT_EV2(i, v)
+#endif
+// Merge-run text moves per scour (host-emulation diagnostic builds only, -DMT_EVGATHER), two
+// counters a slot (low | high 32 bits): 0 scourLeaves calls | of those with a gather, 1 gathers |
+// with an earlier gather in the same call, 2 64-unit chunks gathered, 3 units gathered | calls that
+// load a last unit (lastNL), 4 gathers of more than | of exactly MT_GT_CH * 64 units, 5 calls with
+// three gathers or more | gathers after a gather in a call over three leaf blocks or more
+// (packParent), 6 gathers after a gather and then a run extended in place | gathers into a new
+// region right after one into a head's slack, 7 compactions by a run's plan after a gather in the
+// same call | heads that lose MT_M_NONL.
+#if defined(MT_EVGATHER) && !defined(__HIP_DEVICE_COMPILE__)
+#define MT_EVG_ON 1
+#define MT_EVG(i, hi) prof[i] += 1ull << ((hi) ? 32 : 0)
+#else
+#define MT_EVG_ON 0
+#define MT_EVG(i, hi)
 #endif
 // Range-op events (host-emulation diagnostic builds only, -DMT_EVRANGE): 0 range ops, 1 applied
 // in the start walk's leaf visit (rangeLeaf), 2 start and end boundary in one leaf block,
@@ -1506,8 +1521,9 @@ template <int RES, bool FULL = true> struct MtEngT {
         MT_QB(q0); MT_QC(4);
         int newWin = 0; nU = 0;
         if constexpr (BT) {                               // corrections table: cleared per U set
-            for (int base = 0; base < blkTop; base += MT_WAVE) {
-                const int m = (blkTop - base) < MT_WAVE ? (blkTop - base) : MT_WAVE;
+            const int bt = uni(blkTop);                   // a scalar loop: as a vector one its counter pair took a spill slot
+            for (int base = 0; base < bt; base += MT_WAVE) {
+                const int m = (bt - base) < MT_WAVE ? (bt - base) : MT_WAVE;
                 wave_for(m, [&](int k) MT_LAM { LB().bcorr[base + k] = 0; });
             }
             wave_sync();
@@ -2442,7 +2458,7 @@ template <int RES, bool FULL = true> struct MtEngT {
         }
     }
     MT_HD int pkey(int id, int i) const { return (int)pset[id + (i >> 4)].key[i & 15]; }
-    MT_HD int pval(int id, int i) const { return pset[id + (i >> 4)].val[i & 15]; }
+    MT_HD int pval(int id, int i) const { i = mt_opaque(i); return pset[id + (i >> 4)].val[i & 15]; }   // (mt_opaque: as sc->hold[lane])
     // matchProperties class of a stored value: NaN, undefined and fresh consensus objects
     // (the values below 0) equal nothing, themselves included (MT_VAL_*, include/mtgpu.h).
     MT_HD uint32_t pclass(int v) const { return v >= 0 ? S.p_class[v] : 0xFFFFFFFFu; }
@@ -2519,48 +2535,76 @@ template <int RES, bool FULL = true> struct MtEngT {
         if (textTop + n > (int)S.textCap) { status |= MT_DS_OOM_TEXT; return -1; }
         const int o = textTop; textTop += n; return o;
     }
-    // text[dst, dst + Σ len) = the concatenation of up to 9 pieces: an optional head piece
-    // (hsrc, hlen), then the text of lanes [i0, i1) of (src, len), 64 units a pass (one
-    // load round trip per pass however many pieces).
-    MT_HD void gatherText(int dst, int hsrc, int hlen, const LaneArr<int>& src, const LaneArr<int>& len, int i0, int i1) {
-        int n = hlen;
-        for (int i = i0; i < i1; i++) n += wave_at(len, i);
-        MT_EV2(2, n); MT_EV2(3, 1);
+    // A merge run's text move, as its plan leaves it: text[dst, dst + n) = the concatenation of up
+    // to 9 pieces, an optional head piece (hsrc, hlen), then the text of lanes [i0, i1) of the
+    // scour's (toff, len) lane arrays.  n == 0: nothing moves (the run was extended in place).
+    struct GtPlan { int dst, hsrc, hlen, i0, i1, n; };
+#if MT_EVG_ON
+    int evgN = 0, evgNb = 0, evgLast = 0;   // gathers so far in this scourLeaves call, its blocks, the last run's kind
+    void evgGather(int kind, int n) {       // kind 1: into the head's slack, 2: into a new region
+        if (evgN == 0) MT_EVG(0, 1);
+        MT_EVG(1, 0);
+        if (evgN > 0) MT_EVG(1, 1);
+        prof[2] += (unsigned long long)((n + MT_WAVE - 1) / MT_WAVE); prof[3] += (unsigned long long)n;
+        if (n > MT_GT_CH * MT_WAVE) MT_EVG(4, 0);
+        if (n == MT_GT_CH * MT_WAVE) MT_EVG(4, 1);
+        if (evgN == 2) MT_EVG(5, 0);
+        if (evgN > 0 && evgNb >= 3) MT_EVG(5, 1);
+        if (evgLast == 3) MT_EVG(6, 0);
+        if (evgLast == 1 && kind == 2) MT_EVG(6, 1);
+        evgLast = kind; evgN++;
+    }
+#endif
+    // The loads of up to MT_GT_CH chunks of 64 units of a planned move, from unit `base` on: one
+    // load round trip however many pieces.  The arena is addressed as global memory here and in
+    // gtStore (mt_global): `text` is rebuilt from a pointer read back from LDS, so the compiler
+    // would emit flat_* accesses and wait for every counter to reach zero around each of them.
+    MT_HD void gtLoad(const GtPlan& g, const LaneArr<int>& src, const LaneArr<int>& len, int base, LaneArr<int> (&v)[MT_GT_CH]) {
+        const auto tg = mt_global(text);
+        const int hsrc = g.hsrc, hlen = g.hlen, i0 = g.i0, i1 = g.i1, n = g.n;
         // piece of unit q: scan the (<= 9) piece prefixes, all scalar
-        auto srcOf = [&](int base, int m) MT_LAM {
-            auto from = wave_map(m, [&](int k) MT_LAM { const int q = base + k; return q < hlen ? hsrc + q : -1; });
+        auto srcOf = [&](int b, int m) MT_LAM {
+            auto from = wave_map(m, [&](int k) MT_LAM { const int q = b + k; return q < hlen ? hsrc + q : -1; });
             int pre = hlen;
             for (int i = i0; i < i1; i++) {
                 const int ps = wave_at(src, i), pl = wave_at(len, i), p0 = pre;
                 from = wave_map(m, [&](int k) MT_LAM {
-                    const int q = base + k, f0 = own(from, k);
+                    const int q = b + k, f0 = own(from, k);
                     return (q >= p0 && q < p0 + pl) ? ps + (q - p0) : f0;
                 });
                 pre += pl;
             }
             return from;
         };
-        // The destination never overlaps a source (a new region, or the head's slack past its
-        // text), so MT_GT_CH chunks of 64 units are loaded before any is stored: one round trip
-        // per MT_GT_CH * 64 units instead of one per 64.
-        for (int base = 0; base < n; base += MT_GT_CH * MT_WAVE) {
-            LaneArr<int> v[MT_GT_CH];
 #pragma unroll
-            for (int u = 0; u < MT_GT_CH; u++) {
-                const int b = base + u * MT_WAVE;
-                if (b >= n) break;                                   // uniform: skips the piece scan too
-                const int m = (n - b) < MT_WAVE ? (n - b) : MT_WAVE;
-                const auto from = srcOf(b, m);
-                v[u] = wave_map(m, [&](int k) MT_LAM { return (int)text[own(from, k)]; });
-            }
+        for (int u = 0; u < MT_GT_CH; u++) {
+            const int b = base + u * MT_WAVE;
+            if (b >= n) break;                                   // uniform: skips the piece scan too
+            const int m = (n - b) < MT_WAVE ? (n - b) : MT_WAVE;
+            const auto from = srcOf(b, m);
+            v[u] = wave_map(m, [&](int k) MT_LAM { return (int)tg[own(from, k)]; });
+        }
+    }
+    MT_HD void gtStore(const GtPlan& g, int base, const LaneArr<int> (&v)[MT_GT_CH]) {
+        const auto tg = mt_global(text);
+        const int dst = g.dst, n = g.n;
+#pragma unroll
+        for (int u = 0; u < MT_GT_CH; u++) {
+            const int b = base + u * MT_WAVE;
+            if (b >= n) break;
+            const int m = (n - b) < MT_WAVE ? (n - b) : MT_WAVE;
+            wave_for(m, [&](int k) MT_LAM { tg[dst + b + k] = (uint16_t)own(v[u], k); });
+        }
+    }
+    // A planned move on its own.  The destination never overlaps a source (a new region, or the
+    // head's slack past its text), so MT_GT_CH chunks of 64 units are loaded before any is
+    // stored: one round trip per MT_GT_CH * 64 units instead of one per 64.
+    MT_HD void gatherText(const GtPlan& g, const LaneArr<int>& src, const LaneArr<int>& len) {
+        for (int base = 0; base < g.n; base += MT_GT_CH * MT_WAVE) {
+            LaneArr<int> v[MT_GT_CH] = {};
+            gtLoad(g, src, len, base, v);
             wave_sync();
-#pragma unroll
-            for (int u = 0; u < MT_GT_CH; u++) {
-                const int b = base + u * MT_WAVE;
-                if (b >= n) break;
-                const int m = (n - b) < MT_WAVE ? (n - b) : MT_WAVE;
-                wave_for(m, [&](int k) MT_LAM { text[dst + b + k] = (uint16_t)own(v[u], k); });
-            }
+            gtStore(g, base, v);
         }
         wave_sync();
     }
@@ -2569,11 +2613,13 @@ template <int RES, bool FULL = true> struct MtEngT {
     // head owns [toff, toff + tcap) of the arena: followers whose text already sits right
     // after the head's (split halves coming back together) extend it in place; the rest
     // are copied into the head's slack, or head and rest move together to a new region
-    // of twice the size (amortized O(appended units)).  Returns the head's new length.
-    MT_HD int mergeRun(const LaneArr<int>& f, LaneArr<int>& ft, LaneArr<int>& fc, const LaneArr<int>& fl,
-                       int h, int i0, int i1) {
-        MT_ZB(z2);
-        const int hr = wave_at(f, h);
+    // of twice the size (amortized O(appended units)).
+    // A run is planned in two steps (the scalar decisions apart from the move, so that diagnostic
+    // builds can count them), and its text moved by the caller (scourLeaves).  decideRun
+    // changes nothing: followers [i0, i) extend the head in place to (tp, lp, cp); followers
+    // [i, i1) of `rest` units are copied, into the slack (nc == 0) or a new region of nc units.
+    struct RunPlan { int tp, lp, cp, i, rest, nc; };
+    MT_HD RunPlan decideRun(const LaneArr<int>& ft, const LaneArr<int>& fc, const LaneArr<int>& fl, int h, int i0, int i1) {
         int tp = wave_at(ft, h), lp = wave_at(fl, h), cp = wave_at(fc, h);
         int i = i0;
         for (; i < i1; i++) {                              // in place: no copy
@@ -2581,34 +2627,60 @@ template <int RES, bool FULL = true> struct MtEngT {
             if (!(ts == tp + lp && cp == lp)) break;
             cp = lp + wave_at(fc, i); lp += wave_at(fl, i);
         }
-        if (i < i1) {
-            int rest = 0;
-            for (int j = i; j < i1; j++) rest += wave_at(fl, j);
-            if (lp + rest <= cp) {
-                gatherText(tp + lp, 0, 0, ft, fl, i, i1);
-            } else {
-                int nc = 2 * (lp + rest); if (nc < 16) nc = 16;
-                if (textTop + nc > (int)S.textCap) {
+        int rest = 0, nc = 0;
+        for (int j = i; j < i1; j++) rest += wave_at(fl, j);
+        if (i < i1 && lp + rest > cp) { nc = 2 * (lp + rest); if (nc < 16) nc = 16; }
+        return RunPlan{tp, lp, cp, i, rest, nc};
+    }
+    // A new region of nc units does not fit the live half: commitRun compacts first.
+    MT_HD bool runCompacts(const RunPlan& r) const { return r.nc && textTop + r.nc > (int)S.textCap; }
+    // The move decideRun's plan asks for, but for its destination (commitRun reserves it).
+    MT_HD GtPlan runMove(const RunPlan& r, int i1) const {
+        return GtPlan{r.tp + r.lp, r.nc ? r.tp : 0, r.nc ? r.lp : 0, r.i, i1, r.i < i1 ? (r.nc ? r.lp : 0) + r.rest : 0};
+    }
+    // commitRun reserves the region (compacting first if it must) and writes the head's len /
+    // toff / tcap; it returns the move, of n == 0 units if the arena is full.  Commits are made
+    // in run order, so allocation order and textTop do not depend on when the text moves.
+    MT_HD GtPlan commitRun(const LaneArr<int>& f, LaneArr<int>& ft, LaneArr<int>& fc, const LaneArr<int>& fl,
+                           int h, int i0, int i1, RunPlan r) {
+        const int hr = wave_at(f, h);
+        if (r.i < i1) {
+#if MT_EVG_ON
+            if (r.nc && runCompacts(r) && evgN > 0) MT_EVG(7, 0);
+#endif
+            if (r.nc) {
+                if (runCompacts(r)) {
                     // compaction moves every linked row's text (head and followers apart
                     // again, slack gone): the whole run is copied, exactly sized
                     textGC();
                     ft = wave_map(8 * MT_MAXN, [&](int t) MT_LAM { const int g = own(f, t); return g >= 0 ? row(g).toff : 0; });
                     fc = wave_map(8 * MT_MAXN, [&](int t) MT_LAM { const int g = own(f, t); return g >= 0 ? row(g).tcap : 0; });
-                    tp = wave_at(ft, h); lp = wave_at(fl, h); i = i0;
-                    rest = 0;
-                    for (int j = i; j < i1; j++) rest += wave_at(fl, j);
-                    nc = lp + rest;
+                    r.tp = wave_at(ft, h); r.lp = wave_at(fl, h); r.i = i0;
+                    r.rest = 0;
+                    for (int j = i0; j < i1; j++) r.rest += wave_at(fl, j);
+                    r.nc = r.lp + r.rest;
                 }
-                const int o = textAlloc(nc);
-                if (o < 0) { MT_ZE(2, z2); return lp; }
-                gatherText(o, tp, lp, ft, fl, i, i1);
-                tp = o; cp = nc;
+                const int o = textAlloc(r.nc);
+                if (o < 0) return GtPlan{0, 0, 0, i1, i1, 0};
+                GtPlan g = runMove(r, i1);
+                g.dst = o;
+#if MT_EVG_ON
+                evgGather(2, g.n);
+#endif
+                MT_EV2(2, g.n); MT_EV2(3, 1);
+                row(hr).len = r.lp + r.rest; row(hr).toff = o; row(hr).tcap = r.nc;
+                return g;
             }
-            lp += rest;
+#if MT_EVG_ON
+            evgGather(1, r.rest);
+#endif
+            MT_EV2(2, r.rest); MT_EV2(3, 1);
         }
-        row(hr).len = lp; row(hr).toff = tp; row(hr).tcap = cp;
-        MT_ZE(2, z2);
-        return lp;
+#if MT_EVG_ON
+        else if (evgN > 0) evgLast = 3;
+#endif
+        row(hr).len = r.lp + r.rest; row(hr).toff = r.tp; row(hr).tcap = r.cp;
+        return runMove(r, i1);
     }
     // scourNode (MT/mergeTree.ts:1278-1356) for leaf blocks blks[0..nb) (a lane array,
     // nb <= 7; lane t holds child slot t&7 of block t>>3): kept children are appended to
@@ -2625,6 +2697,9 @@ template <int RES, bool FULL = true> struct MtEngT {
     // run (mergeRun), and unlinks, frees and the hold list are lane-parallel writes.
     MT_HD int scourLeaves(const LaneArr<int>& blks, int nb, int nh) {
         const int span = 8 * nb;
+#if MT_EVG_ON
+        MT_EVG(0, 0); evgN = 0; evgNb = nb; evgLast = 0;
+#endif
         const auto bsel = wave_gather8(blks);       // block id by lane shuffle (per-block scalar arrays spilled)
         auto f = wave_map(span, [&](int t) MT_LAM {
             const int b = own(bsel, t);
@@ -2672,12 +2747,15 @@ template <int RES, bool FULL = true> struct MtEngT {
                 return (((needLast >> t) & 1ull) != 0) & !((uint32_t)own(fm, t) & MT_M_NONL);
             });
             auto lastNL = wave_map(span, [&](int) MT_LAM { return 0; });
-            if (wave_ballot(wave_map(span, [&](int t) MT_LAM { return (bool)own(need, t); })))   // uniform skip
+            if (wave_ballot(wave_map(span, [&](int t) MT_LAM { return (bool)own(need, t); }))) { // uniform skip
+                MT_EVG(3, 1);
+                const auto tg = mt_global(text);
                 lastNL = wave_map(span, [&](int t) MT_LAM {              // per lane branch-free
                     const bool q = own(need, t);
-                    const int last = (int)text[q ? own(ft, t) + own(fl, t) - 1 : 0];
+                    const int last = (int)tg[q ? own(ft, t) + own(fl, t) - 1 : 0];
                     return (q & (last == '\n')) ? 1 : 0;
                 });
+            }
             const auto lastNL1 = wave_from8<-1>(lastNL);
             // matchProperties: equal ids match; a missing map never matches a present one;
             // two different maps compare key by key (propsMatch)
@@ -2736,21 +2814,25 @@ template <int RES, bool FULL = true> struct MtEngT {
                 }
                 if (head >= 0) runLen = wave_set(runLen, head, P);
             }
-            // move the text, one run at a time (followers still linked: compaction keeps their text)
+            // move the text, one run at a time (followers still linked: compaction keeps their text).
+            // Keeping two runs' moves in flight was tried and not kept.
             for (uint64_t m = merged; m;) {
                 const int i0 = __builtin_ctzll(m);
                 int i1 = i0;
                 while ((m >> i1) & 1ull) i1++;
                 m &= ~((i1 >= 64 ? ~0ull : ((1ull << i1) - 1ull)));
-                mergeRun(f, ft, fc, fl, i0 - 1, i0, i1);
+                MT_ZB(z2);
+                const GtPlan g = commitRun(f, ft, fc, fl, i0 - 1, i0, i1, decideRun(ft, fc, fl, i0 - 1, i0, i1));
                 {   // the appended text may carry a newline: the head keeps the flag only if all did
                     const uint32_t hm = (uint32_t)wave_at(fm, i0 - 1);
                     if (hm & MT_M_NONL) {
                         bool all = true;
                         for (int i = i0; i < i1; i++) all = all && ((uint32_t)wave_at(fm, i) & MT_M_NONL);
-                        if (!all) row(wave_at(f, i0 - 1)).meta = hm & ~MT_M_NONL;
+                        if (!all) { MT_EVG(7, 1); row(wave_at(f, i0 - 1)).meta = hm & ~MT_M_NONL; }
                     }
                 }
+                if (g.n) gatherText(g, ft, fl);
+                MT_ZE(2, z2);
             }
         }
         if (FULL && drec) { // maintenance callbacks in child order: UNLINK (:1299-1305), APPEND (:1325-1331)
@@ -2853,7 +2935,7 @@ template <int RES, bool FULL = true> struct MtEngT {
             wave_for(8 * cc, [&](int t) MT_LAM {
                 const int ni = t >> 3, slot = t & 7;
                 const int cnt = base + (ni < extra ? 1 : 0), st = ni * base + (ni < extra ? ni : extra);
-                const int ch = slot < cnt ? sc->hold[st + slot] : -1;
+                const int ch = slot < cnt ? sc->hold[st + mt_opaque(slot)] : -1;
                 const int NB = own(nb8, t);
                 bk(NB).c[slot] = ch;
                 if ((int)(ch >= 0) & (int)(own(ob, t) != NB)) setChildParent(chh, ch, NB);
@@ -3109,6 +3191,7 @@ template <int RES, bool FULL = true> struct MtEngT {
                           wave_ballot(wave_map(nn, [&](int i) MT_LAM { return own(vv, i) < 0; })) ? 1 : 0;
         if (never) mt_cold_v.pNever = 1;
         wave_for(nch * MT_PSK, [&](int i) MT_LAM {
+            i = mt_opaque(i);                                // the lane's offset into the map is not kept from the kernel's entry
             pset[id + (i >> 4)].key[i & 15] = (uint16_t)(i < nn ? own(kk, i) : 0);
             pset[id + (i >> 4)].val[i & 15] = i < nn ? own(vv, i) : 0;
         });

@@ -105,9 +105,13 @@ __device__ __forceinline__ int wave_incl_scan8(int v) {
 }
 __device__ __forceinline__ int wave_sum8(int v) { return __builtin_amdgcn_readlane(wave_incl_scan8(v), 7); }
 __device__ __forceinline__ int wave_excl_scan8(int v) { return wave_incl_scan8(v) - v; }
+// the same value, opaque to the compiler: lane-index arithmetic behind it is not hoisted to the
+// kernel's entry (where it would hold a VGPR, or a spill slot, across the whole replay loop)
+__device__ __forceinline__ int mt_opaque(int v) { __asm__ volatile("" : "+v"(v)); return v; }
 // lane i receives a[i + off] (0 outside [0, 64)); call from uniform control flow
+// (mt_opaque: the shuffle's lane address is made here, not kept from the kernel's entry)
 __device__ __forceinline__ int wave_from(int a, int off) {
-    const int src = __lane_id() + off;
+    const int src = mt_opaque((int)__lane_id()) + off;
     const int v = __shfl(a, src & 63);
     return (src >= 0 && src < 64) ? v : 0;
 }
@@ -127,9 +131,11 @@ __device__ __forceinline__ int wave_set(int a, int k, int v) { return __lane_id(
 __device__ __forceinline__ void lds_add(int* p, int v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 // keeps a loaded value alive (a prefetch whose result is otherwise unused)
 __device__ __forceinline__ void mt_keep(int v) { __asm__ volatile("" ::"v"(v)); }
-// the same value, opaque to the compiler: lane-index arithmetic behind it is not hoisted to the
-// kernel's entry (where it would hold a VGPR, or a spill slot, across the whole replay loop)
-__device__ __forceinline__ int mt_opaque(int v) { __asm__ volatile("" : "+v"(v)); return v; }
+// the same pointer, typed as global memory at its use site: the accesses through it are global_*
+// instructions, which the compiler may leave in flight behind a counted vmcnt wait (after a flat_*
+// access, whose home it does not know, it waits for every counter to reach zero)
+template <class T> using MtGlobal = __attribute__((address_space(1))) T;
+template <class T> __device__ __forceinline__ MtGlobal<T>* mt_global(T* p) { return (MtGlobal<T>*)p; }
 // per-lane compare-and-swap on LDS; returns the old value
 __device__ __forceinline__ int lds_cas(int* p, int cmp, int v) {
     __hip_atomic_compare_exchange_strong(p, &cmp, v, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -235,6 +241,7 @@ inline void lds_add(int* p, int v) { *p += v; }
 inline int lds_cas(int* p, int cmp, int v) { const int o = *p; if (o == cmp) *p = v; return o; }
 inline void mt_keep(int) {}
 inline int mt_opaque(int v) { return v; }
+template <class T> inline T* mt_global(T* p) { return p; }
 inline unsigned long long wave_atomic_add(unsigned long long* p, unsigned long long d) { return __atomic_fetch_add(p, d, __ATOMIC_RELAXED); }
 inline unsigned long long wave_atomic_next(unsigned long long* p) { return wave_atomic_add(p, 1ull); }
 inline unsigned long long wave_sum64(const LaneArr<unsigned long long>& a) {
